@@ -1,11 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): node GFLOPS of the range-partitioned,
-load-balanced bf16 SGEMM 8192³ across N MI355X (one process per GPU), plus the
-Mandelbrot 4096² event-pipeline number and the load-balancer convergence
-count ("load-balance iters") as extra fields.
+load-balanced bf16 SGEMM 8192³ across N MI355X (one process per GPU).  With
+``--full`` also the Mandelbrot 4096² event-pipeline number, the load-balancer
+convergence count ("load-balance iters") and every other config, as extra
+fields.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (N > 1)
+
+A plain run sets up (inputs, balancer to convergence, 100 untimed computes
+for the clocks), makes W warm-up
+computes, times K computes, writes its outputs if asked and prints the result
+line: nothing else.  ``--dump-outputs DIR`` writes ``DIR/c.npy``: the C that
+the timed computes left in device memory, row-major fp32, a fixed seeded
+choice of 1024 of its rows (32 MiB at 8192³; every row of a small C).  The
+inputs are seeded, so two builds run with the same arguments can be compared
+element for element.
 
 Without a torchrun environment, ``--gpus N > 1`` starts the N rank processes
 itself: ``torch.distributed.run`` runs as a child process of this one, which
@@ -17,19 +27,24 @@ framework: the balancer splits the 1024 (or 2048) output tiles across the
 ranks, every rank runs the hand-written CDNA4 MFMA kernel on its slice, the
 per-device times are exchanged and the next split is computed.  Inputs are
 device-resident after the first call and C stays in device memory
-(BASELINE.md "device-resident"); the host-resident variant (A/B uploaded and
-C slices downloaded each call) is reported separately.  Data: synthetic
-uniform [-1, 1) bf16.  After the timed loops every rank downloads its device
-replica of C and compares EVERY tile of its own range with a float64 product
-computed by torch on its GPU (``GemmBf16.verify_full``); the bench exits
-non-zero when the relative error exceeds 1e-4 (measured: ~1.5e-6).
+(BASELINE.md "device-resident").  Data: synthetic uniform [-1, 1) bf16.
+
+``--full`` goes on after the headline: the same GEMM with a host sync per
+step, on async queues and host-resident (A/B uploaded and C slices
+downloaded each call), each reported separately; every rank downloads its
+device replica of C and compares EVERY tile of its own range with a float64
+product computed by torch on its GPU (``GemmBf16.verify_full``), and the
+bench exits non-zero when the relative error exceeds 1e-4 (measured:
+~1.5e-6); then Mandelbrot, the row-major / hipBLASLt comparison, the
+load-balance iters, the per-GPU slices, the node configs (child processes)
+and the peer topology.
 
 Rank 0 prints ONE compact JSON line (< 6 KB, so a log tail keeps it whole):
 the headline fields, then ``extra`` with one short summary per config and
 the metric's own components LAST (``load_balance_iters``,
-``mandelbrot_4k``, ``sgemm``).  Everything measured — per-round arrays,
-predictor fits, placements — goes to ``--detail`` (default
-``gpurun_out/bench_detail_n{N}.json`` and ``profiles/bench_detail_n{N}.json``).
+``mandelbrot_4k``, ``sgemm``); what a plain run did not measure is null.
+Everything measured — per-round arrays, predictor fits, placements — goes to
+``--detail`` (with ``--full`` it has a default, see :func:`write_detail`).
 
 In a container without a GPU the headline runs a plain kernel-string GEMM on
 each rank's CPU device instead (``"device": "cpu"`` in the config): that is
@@ -128,7 +143,58 @@ def _converge(ctx, cr, step, compute_id: int, max_calls: int = 40, stable: int =
     return max_calls
 
 
-def bench_sgemm(ctx, steps, warmup, size=8192, tile=None):
+DUMP_ROWS = 1024  # --dump-outputs keeps this many rows of C (8192 fp32 columns: 32 MiB)
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 0
+
+
+def _dump_rows(m: int, n: int) -> np.ndarray:
+    """The rows of an m×n fp32 C that ``--dump-outputs`` keeps: all of them
+    while they fit, else a fixed, seeded choice (every tile column and, at
+    the headline size, ~32 rows of every tile row), in ascending order."""
+    keep = max(1, min(m, DUMP_ROWS, DUMP_MAX_BYTES // (4 * n)))
+    if keep == m:
+        return np.arange(m)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(m, size=keep, replace=False))
+
+
+def _sum_array_over_ranks(ctx, a: np.ndarray) -> np.ndarray:
+    if not ctx.is_distributed:
+        return a
+    import torch
+    import torch.distributed as dist
+
+    dev = torch.device("cuda", torch.cuda.current_device()) if (
+        dist.get_backend() == "nccl") else torch.device("cpu")
+    t = torch.from_numpy(a).to(dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu().numpy()
+
+
+def _c_sample(ctx, g) -> np.ndarray:
+    """The sampled rows of the row-major C that the last compute left on the
+    devices.  Every rank downloads the slices its devices own (the rest of
+    its host C is zeroed first) and the ranks' samples are summed, so each
+    element comes from the device that computed it."""
+    g.C.array[:] = 0
+    sample = np.ascontiguousarray(g.result(download=True)[_dump_rows(g.M, g.N)], dtype=np.float32)
+    return _sum_array_over_ranks(ctx, sample)
+
+
+def write_outputs(ctx, directory: str, arrays: dict) -> None:
+    """``--dump-outputs``: rank 0 writes each array as ``<name>.npy``."""
+    if ctx.rank != 0:
+        return
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def bench_sgemm(ctx, steps, warmup, size=8192, tile=None, full=False, dump=False):
+    """The headline: ``warmup`` computes, then ``steps`` timed computes in
+    enqueue mode on one queue.  ``dump``: the result carries ``c_sample``,
+    the sampled rows of the C those steps left on the devices.  ``full``
+    adds every other schedule of the same GEMM and the whole-output checks."""
     from cekirdekler_amd.ops.gemm import GemmBf16
     from cekirdekler_amd.ops.library import library
     from cekirdekler_amd.parallel.distributed import DistributedCruncher
@@ -158,10 +224,32 @@ def bench_sgemm(ctx, steps, warmup, size=8192, tile=None):
     # computes run in enqueue mode (reference ClNumberCruncher.enqueueMode:
     # no host sync between computes, split frozen, timings gathered when the
     # mode is left) — every step still runs the whole GEMM on every device.
+    enter = lambda: setattr(cr, "enqueue_mode", True)  # noqa: E731
+    leave = lambda: setattr(cr, "enqueue_mode", False)  # noqa: E731
+    if not full:  # a plain run: the W warm-up computes, the K timed ones, nothing else
+        # set-up, clocks: a --full run makes K synced computes before its
+        # timed loop, and the first computes after set-up run slow (20 timed
+        # steps after 9 computes: 1.42 PF, the parent's 30: 1.50).  A plain
+        # run makes a fixed number instead (the same on every rank: each
+        # compute exchanges timings).  20 timed steps, runs taking turns on
+        # one GPU: 1.50 PF after 100, 1.45-1.49 after 400, 1.46 for --full
+        _sync()  # torch creates its device context at its first call: here, not between warm-up and timing (1-2 % slower there)
+        for _ in range(SETTLE_COMPUTES):
+            step()
+        ms = timed(ctx, step, steps, warmup, enter=enter, leave=leave)
+        out = {"ms": ms, "gflops": g.flops / (ms * 1e-3) / 1e9, "tile": tile,
+               "timing": "enqueue mode, one queue (one GEMM in flight)", "balancer_setup_calls": converge,
+               "ranges": cr.ranges(1), "tiles_total": g.tiles, "device": "gpu"}
+        out["single_queue"] = {k: out[k] for k in ("ms", "gflops", "tile")}
+        if dump:
+            out["c_sample"] = _c_sample(ctx, g)
+        cr.dispose()
+        for a in (g.A, g.B, g.C, g.dims, *g.extra):
+            a.dispose()
+        return out
     ms_sync = timed(ctx, step, steps, warmup)  # one host sync + time exchange per compute
-    ms = timed(ctx, step, steps, 1,
-               enter=lambda: setattr(cr, "enqueue_mode", True),
-               leave=lambda: setattr(cr, "enqueue_mode", False))
+    ms = timed(ctx, step, steps, 1, enter=enter, leave=leave)
+    c_sample = _c_sample(ctx, g) if dump else None
     ranges = cr.ranges(1)
     # the same computes once more with dispatch-stamped kernel times: the
     # GEMM kernel alone, without the gap between back-to-back launches that
@@ -284,7 +372,7 @@ def bench_sgemm(ctx, steps, warmup, size=8192, tile=None):
     best = single
     timing = "enqueue mode, one queue (one GEMM in flight)"
     return {"ms": best["ms"], "gflops": best["gflops"], "tile": best["tile"], "timing": timing,
-            "single_queue": single, "async_queues": overlapped, "balancer_setup_calls": converge,
+            **({"c_sample": c_sample} if dump else {}), "single_queue": single, "async_queues": overlapped, "balancer_setup_calls": converge,
             "sync_per_step_ms": ms_sync, "sync_per_step_gflops": g.flops / (ms_sync * 1e-3) / 1e9,
             "host_resident_ms": ms_host, "host_resident_gflops": g.flops / (ms_host * 1e-3) / 1e9,
             "host_resident_blobs": blobs, "host_resident_calls_ms": [round(x, 3) for x in host_calls],
@@ -309,12 +397,13 @@ __global__ void gemm_nt(const int* d, const float* a, const float* b, float* c) 
 """
 
 
-def bench_sgemm_cpu(ctx, steps, warmup, size=256):
+def bench_sgemm_cpu(ctx, steps, warmup, size=256, full=False, dump=False):
     """GPU-less rehearsal of the headline: the same range-partitioned,
     balanced compute() over one CPU device per rank (plain fp32 kernel
     string, one work item per output element, C device-resident after the
     first call).  Exercises the rank launcher, the shared-memory control
-    plane and the identical-split property, not the MI355X kernel."""
+    plane and the identical-split property, not the MI355X kernel.
+    ``full`` adds the check of this rank's range against a float64 product."""
     import cekirdekler_amd as ck
     from cekirdekler_amd.parallel.distributed import DistributedCruncher
 
@@ -337,16 +426,22 @@ def bench_sgemm_cpu(ctx, steps, warmup, size=256):
     ranges = cr.ranges(1)
     lo = cr.references(1)[ctx.rank]
     hi = lo + ranges[ctx.rank]
-    ref = (a.array.reshape(size, size).astype(np.float64) @ b.array.reshape(size, size).astype(np.float64).T).ravel()
-    err = float(np.max(np.abs(c.array[lo:hi] - ref[lo:hi])) / max(np.max(np.abs(ref)), 1e-30)) if hi > lo else 0.0
-    err = _max_over_ranks(ctx, err)
-    cr.dispose()
     flops = 2.0 * size ** 3
-    return {"ms": ms, "gflops": flops / (ms * 1e-3) / 1e9, "tile": "cpu-naive", "balancer_setup_calls": converge,
-            "sync_per_step_ms": ms, "sync_per_step_gflops": flops / (ms * 1e-3) / 1e9,
-            "host_resident_ms": ms, "host_resident_gflops": flops / (ms * 1e-3) / 1e9,
-            "ranges": ranges, "max_rel_err": err, "handover_fallbacks": 0, "device": "cpu",
-            "tiles_checked": size * size, "tiles_total": size * size}
+    out = {"ms": ms, "gflops": flops / (ms * 1e-3) / 1e9, "tile": "cpu-naive", "balancer_setup_calls": converge,
+           "sync_per_step_ms": ms, "sync_per_step_gflops": flops / (ms * 1e-3) / 1e9,
+           "host_resident_ms": ms, "host_resident_gflops": flops / (ms * 1e-3) / 1e9,
+           "ranges": ranges, "handover_fallbacks": 0, "device": "cpu", "tiles_total": size * size}
+    if dump:
+        own = np.zeros(size * size, np.float32)  # this rank's range of C, the other ranks' left zero
+        own[lo:hi] = c.array[lo:hi]
+        out["c_sample"] = _sum_array_over_ranks(ctx, np.ascontiguousarray(own.reshape(size, size)[_dump_rows(size, size)]))
+    if full:
+        ref = (a.array.reshape(size, size).astype(np.float64) @ b.array.reshape(size, size).astype(np.float64).T).ravel()
+        err = float(np.max(np.abs(c.array[lo:hi] - ref[lo:hi])) / max(np.max(np.abs(ref)), 1e-30)) if hi > lo else 0.0
+        out["max_rel_err"] = _max_over_ranks(ctx, err)
+        out["tiles_checked"] = size * size
+    cr.dispose()
+    return out
 
 
 def _all_ranges(ctx, ranges):
@@ -675,6 +770,7 @@ def bench_node_configs(world: int) -> dict:
     return out
 
 
+SETTLE_COMPUTES = 100  # bench_sgemm, plain run: untimed computes after the balancer has converged
 SLICE_ROUNDS = 5  # bench_sgemm_slices: timed rounds per slice (median)
 SLICE_WARMUP_S = 0.3  # bench_sgemm_slices: untimed GEMMs per slice before timing
 MAX_REL_ERR = 1e-4  # bf16 inputs, fp32 accumulation: measured ~1.5e-6 relative to max |ref| per tile
@@ -903,11 +999,18 @@ def parse_args(argv=None):
     ap.add_argument("--tile", default=None)
     ap.add_argument("--device", choices=("auto", "gpu", "cpu"), default="auto",
                     help="cpu: kernel-string GEMM on each rank's CPU device (launcher rehearsal)")
-    ap.add_argument("--skip-mandelbrot", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: the other schedules of the "
+                         "GEMM, whole-output checks, Mandelbrot, load-balance iters, slices, node configs, peers")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the C of the last timed step (a fixed, seeded sample of its rows, fp32) "
+                         "as DIR/c.npy")
+    ap.add_argument("--skip-mandelbrot", action="store_true", help="with --full: no Mandelbrot config")
     ap.add_argument("--skip-node-configs", action="store_true",
-                    help="skip the N-body pipeline and task-pool configs (rank 0, after the headline)")
+                    help="with --full: skip the N-body pipeline and task-pool configs (rank 0, after the headline)")
     ap.add_argument("--detail", default=None,
-                    help="path of the full results JSON (default: gpurun_out/ and profiles/bench_detail_n{N}.json)")
+                    help="path of the results JSON (default: with --full only, bench_detail_n{N}.json "
+                         "in the places write_detail() lists)")
     return ap.parse_args(argv)
 
 
@@ -939,14 +1042,19 @@ def main(argv=None) -> int:
     if ctx.world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the job has {ctx.world} ranks")
     use_gpu = args.device == "gpu" or (args.device == "auto" and gpu_available())
+    dump = args.dump_outputs is not None
     if use_gpu:
-        sg = bench_sgemm(ctx, args.steps, args.warmup, args.size, args.tile)
+        sg = bench_sgemm(ctx, args.steps, args.warmup, args.size, args.tile, full=args.full, dump=dump)
     else:
-        sg = bench_sgemm_cpu(ctx, args.steps, args.warmup, min(args.size, 512))
+        sg = bench_sgemm_cpu(ctx, args.steps, args.warmup, min(args.size, 512), full=args.full, dump=dump)
+    if dump:
+        write_outputs(ctx, args.dump_outputs, {"c": sg.pop("c_sample")})
     all_ranges = _all_ranges(ctx, sg["ranges"])
-    mb = {} if (args.skip_mandelbrot or not use_gpu) else bench_mandelbrot(ctx, args.steps, args.warmup)
+    # a plain run ends with the headline; everything below is --full
+    use_gpu_full = use_gpu and args.full
+    mb = {} if (args.skip_mandelbrot or not use_gpu_full) else bench_mandelbrot(ctx, args.steps, args.warmup)
     rowc = {}
-    if ctx.rank == 0 and use_gpu and args.size == 8192:
+    if ctx.rank == 0 and use_gpu_full and args.size == 8192:
         try:  # an extra: a failure is reported in its field
             rowc = _row_major_comparison(args.steps)
         except Exception as e:  # pragma: no cover
@@ -960,21 +1068,21 @@ def main(argv=None) -> int:
         others = [p for r, p in enumerate(pids) if r != ctx.rank]
         dist.barrier()
         dist.destroy_process_group()  # the other ranks exit here; rank 0 goes on alone
-    if ctx.rank == 0 and others:
+    if ctx.rank == 0 and others and args.full:
         # the timing measurements below start once the other ranks have gone
         # (their teardown, 7 GPU contexts when ranks share a GPU, disturbed
         # 10 calls of the load-balance measurement in an 8-rank rehearsal)
         _wait_for_exit(others, timeout_s=60.0)
-    lb = bench_lb_iters() if (ctx.rank == 0 and use_gpu) else {}
+    lb = bench_lb_iters() if (ctx.rank == 0 and use_gpu_full) else {}
     slices = {}
-    if ctx.rank == 0 and use_gpu and args.size == 8192:
+    if ctx.rank == 0 and use_gpu_full and args.size == 8192:
         try:  # an extra: a failure is reported in its field
             slices = bench_sgemm_slices(args.steps)
         except Exception as e:  # pragma: no cover
             slices = {"error": repr(e)[:300]}
-    node = {} if (ctx.rank != 0 or args.skip_node_configs or not use_gpu) else bench_node_configs(ctx.world)
-    peers = _peer_topology(ctx.world) if (ctx.rank == 0 and use_gpu) else {}
-    ok = sg["max_rel_err"] <= MAX_REL_ERR
+    node = {} if (ctx.rank != 0 or args.skip_node_configs or not use_gpu_full) else bench_node_configs(ctx.world)
+    peers = _peer_topology(ctx.world) if (ctx.rank == 0 and use_gpu_full) else {}
+    ok = not args.full or sg["max_rel_err"] <= MAX_REL_ERR  # a plain run checks nothing
     if ctx.rank == 0:
         size = args.size if use_gpu else min(args.size, 512)
         full = {
@@ -983,7 +1091,7 @@ def main(argv=None) -> int:
             **node,
             "peer_topology": peers,
         }
-        detail = write_detail(full, ctx.world, args.detail, gpu=use_gpu)
+        detail = write_detail(full, ctx.world, args.detail, gpu=use_gpu) if (args.full or args.detail) else ""
         out = {
             "metric": METRIC,
             "value": round(sg["gflops"], 1),

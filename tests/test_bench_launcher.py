@@ -21,7 +21,7 @@ def test_bench_spawns_n_ranks_with_identical_splits(n, tmp_path):
     env["CEK_CPU_THREADS"] = "1" if n >= 8 else "2"
     detail = tmp_path / "detail.json"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2",
-                        "--warmup", "1", "--size", "128", "--device", "cpu", "--detail", str(detail)],
+                        "--warmup", "1", "--size", "128", "--device", "cpu", "--full", "--detail", str(detail)],
                        cwd="/tmp", env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -39,6 +39,94 @@ def test_bench_spawns_n_ranks_with_identical_splits(n, tmp_path):
     assert out["steps"] == 2 and out["warmup"] == 1
     full = json.loads(detail.read_text())
     assert full["sgemm"]["ranges"] == sg["ranges"] and len(full["sgemm_ranges_all_ranks"]) == n
+
+
+def _run_bench(*argv, timeout=300):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv],
+                       cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def _cpu_inputs(size):
+    """bench_sgemm_cpu's seeded A and B."""
+    import numpy as np
+
+    rng = np.random.default_rng(0)
+    a = rng.uniform(-1, 1, size * size).astype(np.float32).reshape(size, size)
+    b = rng.uniform(-1, 1, size * size).astype(np.float32).reshape(size, size)
+    return a, b
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_output(tmp_path):
+    """A plain run prints the headline fields, measures and checks nothing
+    else, writes no detail file unless asked, and ``--dump-outputs`` writes
+    the C of the timed computes: equal to the float64 product of the seeded
+    inputs within fp32 rounding of a 96-term sum, and identical from run to
+    run and between one rank and two."""
+    import numpy as np
+
+    size = 96
+    outs = []
+    for name, gpus in (("a", 1), ("b", 1), ("c", 2)):
+        out = _run_bench("--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--size", str(size),
+                         "--device", "cpu", "--dump-outputs", str(tmp_path / name))
+        assert sorted(os.listdir(tmp_path / name)) == ["c.npy"]
+        outs.append(np.load(tmp_path / name / "c.npy"))
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 2
+    assert out["unit"] == "GFLOPS" and out["higher_is_better"] is True and out["dtype"] == "fp32"
+    assert out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(2.0 * size ** 3 / (out["ms_per_step"] * 1e-3) / 1e9, rel=0.02)
+    ex = out["extra"]
+    assert list(ex)[-3:] == ["load_balance_iters", "mandelbrot_4k", "sgemm"]
+    assert ex["detail_file"] == "" and ex["load_balance_iters"] is None and ex["mandelbrot_4k"] is None
+    assert ex["sgemm"]["max_rel_err_full"] is None and ex["sgemm"]["tiles_checked"] is None  # nothing checked
+    assert sum(ex["sgemm"]["ranges"]) == size * size
+    c = outs[0]
+    assert c.dtype == np.float32 and c.shape == (size, size)
+    assert np.array_equal(c, outs[1]) and np.array_equal(c, outs[2])
+    a, b = _cpu_inputs(size)
+    ref = a.astype(np.float64) @ b.astype(np.float64).T
+    # |error| <= K * 2^-24 * sum |a_k b_k| for a sequential fp32 sum of K terms
+    bound = size * 2.0 ** -24 * (np.abs(a).astype(np.float64) @ np.abs(b).astype(np.float64).T)
+    assert np.all(np.abs(c - ref) <= bound)
+
+
+def test_dump_rows_are_a_fixed_sample_within_the_size_limit():
+    import numpy as np
+
+    bench = _bench_module()
+    rows = bench._dump_rows(8192, 8192)
+    assert len(rows) * 8192 * 4 <= 64 << 20 and len(set(rows.tolist())) == len(rows) == 1024
+    assert np.array_equal(rows, bench._dump_rows(8192, 8192)) and np.all(np.diff(rows) > 0)
+    assert set((rows // 256).tolist()) == set(range(32))  # every 256-row tile row is sampled
+    assert np.array_equal(bench._dump_rows(512, 512), np.arange(512))
+
+
+@pytest.mark.gpu
+def test_plain_gpu_run_dumps_the_timed_gemm_output(tmp_path):
+    """On the GPU: 4 × 4 tiles of the MFMA kernel (1024³, the split-K tile
+    the bench picks when a slice has fewer tiles than CUs), the dumped C
+    against the float64 product of the same seeded bf16 inputs, within the
+    bench's own bound (relative to max |ref|)."""
+    import numpy as np
+
+    import cekirdekler_amd as ck
+    from cekirdekler_amd.ops.gemm import GemmBf16
+
+    out = _run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "1024",
+                     "--dump-outputs", str(tmp_path), timeout=120)
+    assert out["dtype"] == "bf16" and out["steps"] == 2 and out["config"]["device"] == "gpu"
+    assert out["extra"]["mandelbrot_4k"] is None and out["extra"]["sgemm"]["max_rel_err_full"] is None
+    c = np.load(tmp_path / "c.npy")
+    assert c.dtype == np.float32 and c.shape == (1024, 1024)
+    g = GemmBf16(1024, 1024, 1024, devices=ck.ClPlatforms.all().gpus()[0])  # the same seed: the same A and B
+    ref = g.reference()
+    g.cr.dispose()
+    assert float(np.max(np.abs(c - ref)) / np.max(np.abs(ref))) <= _bench_module().MAX_REL_ERR
 
 
 def test_bench_rejects_world_mismatch():
