@@ -37,8 +37,8 @@ Cores::Cores(const std::vector<DeviceInfo>& devices, const std::string& source,
       error_code_ = 1;
       continue;
     }
-    workers_.emplace_back(new Worker(d, prog, cfg.queue_concurrency, cfg.no_pipelining,
-                                     d.type == kGPU ? 0 : cpu_slot++));
+    workers_.emplace_back(new Worker(d, prog, static_cast<int>(workers_.size()), cfg.queue_concurrency,
+                                     cfg.no_pipelining, d.type == kGPU ? 0 : cpu_slot++));
   }
   error_ = errs.str();
   if (workers_.empty() && error_code_ == 0) {
@@ -818,9 +818,7 @@ void Cores::launch_kernels(Worker& wk, hipStream_t s, const ComputeCall& c, long
     launch_kernels_body(wk, s, c, ref, range);
     return;
   }
-  int dev = 0;
-  while (dev < num_devices() && workers_[dev].get() != &wk) ++dev;
-  PendingSpan sp{dev, c.compute_id, nullptr, nullptr, 0, 0};
+  PendingSpan sp{wk.index(), c.compute_id, nullptr, nullptr, 0, 0};
   if (wk.gpu()) {
     CEK_HIP(hipEventCreateWithFlags(&sp.begin, kTimingEventFlags));
     CEK_HIP(hipEventCreateWithFlags(&sp.end, kTimingEventFlags));
@@ -938,8 +936,7 @@ bool Cores::one_span_per_batch() const {
 
 void Cores::span_begin(Worker& wk, hipStream_t s) {
   if (!wk.gpu() || !spans_on()) return;
-  const int w = worker_index(wk);
-  DevSpans& d = spans_[w];
+  DevSpans& d = spans_[wk.index()];
   if (one_span_per_batch()) {
     // no event marker sits between two back-to-back computes of the batch
     if (d.used > 0) return;
@@ -972,7 +969,7 @@ void Cores::span_begin(Worker& wk, hipStream_t s) {
 
 void Cores::span_end(Worker& wk, hipStream_t s) {
   if (!wk.gpu() || !spans_on()) return;
-  DevSpans& d = spans_[worker_index(wk)];
+  DevSpans& d = spans_[wk.index()];
   if (one_span_per_batch()) return;  // closed at the mode's end
   const int i = enqueue_mode_ ? d.used - 1 : 0;
   if (i < 0) return;
@@ -1036,12 +1033,6 @@ double Cores::enqueue_spans_ms(int w) {
     }
   }
   return total + (ce - cb);
-}
-
-int Cores::worker_index(const Worker& wk) const {
-  for (int i = 0; i < num_devices(); ++i)
-    if (workers_[i].get() == &wk) return i;
-  return -1;
 }
 
 uint64_t Cores::stage_peer_reads(const ComputeCall& c, const std::vector<long long>& ranges,
@@ -1148,15 +1139,13 @@ uint64_t Cores::stage_peer_reads(const ComputeCall& c, const std::vector<long lo
 
 void Cores::full_reads(Worker& wk, hipStream_t s, const ComputeCall& c, uint64_t* h2d) {
   const bool dist = comm_ && dist_broadcast_reads;
-  const int w = worker_index(wk);
-  if (w >= 0 && w < static_cast<int>(staged_dev_.size()) && staged_dev_[w] && s != wk.main_stream())
-    CEK_HIP(hipStreamWaitEvent(s, peer_ready_[w], 0));  // staged on the main stream
+  const int w = wk.index();
+  const bool staged = w < static_cast<int>(staged_dev_.size()) && staged_dev_[w];
+  if (staged && s != wk.main_stream()) CEK_HIP(hipStreamWaitEvent(s, peer_ready_[w], 0));  // staged on the main stream
   for (size_t i = 0; i < c.arrays.size(); ++i) {
     const auto& a = c.arrays[i];
     if (a.zc || a.partial || !a.read) continue;
-    if (w >= 0 && w < static_cast<int>(staged_dev_.size()) && staged_dev_[w] && i < staged_arr_.size() &&
-        staged_arr_[i])
-      continue;  // already staged by the xGMI fan-out
+    if (staged && i < staged_arr_.size() && staged_arr_[i]) continue;  // already staged by the xGMI fan-out
     if (comm_ && dist_split_reads) {
       // Split upload + all-gather (every rank's host copy holds the same
       // data): rank g copies chunk g of the array over its own PCIe link,
@@ -1222,9 +1211,7 @@ bool Cores::defer_downloads(const Worker& wk) const {
 // or touch the same array (a stale host copy going up over the result, or
 // the next upload reading host memory the download has not filled yet).
 bool Cores::must_flush_before(const Worker& wk, hipStream_t s, const ComputeCall& c) const {
-  const int w = worker_index(wk);
-  if (w < 0 || w >= static_cast<int>(pending_d2h_.size())) return false;
-  for (const auto& p : pending_d2h_[w]) {
+  for (const auto& p : pending_d2h_[wk.index()]) {
     if (p.s == s) return true;
     for (const auto& a : c.arrays)
       if (!a.zc && a.uid == p.a.uid) return true;
@@ -1236,8 +1223,7 @@ bool Cores::must_flush_before(const Worker& wk, hipStream_t s, const ComputeCall
 // runs on) and that compute `c`, `next` also waits for every pending
 // download on another stream whose array the compute touches.
 void Cores::flush_downloads(Worker& wk, hipStream_t next, const ComputeCall* c) {
-  const int w = worker_index(wk);
-  if (w < 0 || w >= static_cast<int>(pending_d2h_.size())) return;
+  const int w = wk.index();
   auto& pd = pending_d2h_[w];
   auto& ps = pending_span_end_[w];
   if (pd.empty() && ps.empty()) return;
@@ -1271,11 +1257,101 @@ void Cores::flush_downloads(Worker& wk, hipStream_t next, const ComputeCall* c) 
   ps.clear();
 }
 
+// One device's part of one compute(): the transfers, kernel batches and event
+// edges of the run_* functions below go through this object, which makes the
+// HIP call (on a GPU) and writes the schedule-log line from the same
+// arguments, so the log the schedule checker reads cannot drift from what was
+// issued.  Event slots are taken in call order.  The pipelines log; the
+// 3-phase path never did and stays unlogged.  A stack value per call: no
+// allocation, the slice rules are inlined lambdas
+//   rule(array, begin, count) -> false: this array does not move here
+struct Cores::Ordering {
+  Cores& cs;
+  Worker& wk;
+  const int gidx;
+  const ComputeCall& c;
+  uint64_t& up;    // bytes host → device
+  uint64_t& down;  // bytes device → host
+  const bool logged;
+  int slot = 0;
+
+  void log(const char* op, Lane l, long long off, long long len, int event = -1) {
+    if (logged) cs.log_op(gidx, op, l.id, off, len, event);
+  }
+  // an event on `from`, for work items [off, off + len): returns its slot
+  int mark(Lane from, long long off, long long len, bool issue = true) {
+    const int e = slot++;
+    if (issue && wk.gpu()) CEK_HIP(hipEventRecord(wk.event(e), from.s));
+    log("rec", from, off, len, e);
+    return e;
+  }
+  void wait(Lane to, int e, long long off, long long len, bool issue = true) {
+    if (issue && wk.gpu()) CEK_HIP(hipStreamWaitEvent(to.s, wk.event(e), 0));
+    log("wait", to, off, len, e);
+  }
+  // `to` goes on after what `from` holds so far.  One in-order stream under
+  // both names needs no event: the edge is logged and its slot consumed only.
+  void link(Lane from, Lane to, long long off, long long len) {
+    const bool issue = from.s != to.s;
+    wait(to, mark(from, off, len, issue), off, len, issue);
+  }
+  void full_reads(Lane l) {
+    cs.full_reads(wk, l.s, c, &up);
+    log("h2d", l, -1, -1);
+  }
+  template <class Rule>
+  void h2d(Lane l, long long off, long long len, Rule rule) {
+    for (auto& a : c.arrays) {
+      uint64_t b, n;
+      if (a.zc || !a.partial || !rule(a, b, n)) continue;
+      wk.h2d(l.s, a, b, n);
+      up += n * a.elem_size;
+    }
+    log("h2d", l, off, len);
+  }
+  void kernels(Lane l, long long off, long long len) {
+    cs.launch_kernels(wk, l.s, c, off, len);
+    log("kernel", l, off, len);
+  }
+  template <class Rule>
+  void d2h(Lane l, long long off, long long len, Rule rule) {
+    for (auto& a : c.arrays) {
+      uint64_t b, n;
+      if (a.zc || !a.write || a.write_all || !rule(a, b, n)) continue;
+      wk.d2h(l.s, a, b, n);
+      down += n * a.elem_size;
+    }
+    log("d2h", l, off, len);
+  }
+  // array i's owner (device i mod D) downloads the whole array
+  bool owns(size_t i) const { return static_cast<int>(i % cs.global_devices_) == gidx; }
+  void write_all_downloads(Lane l) {
+    for (size_t i = 0; i < c.arrays.size(); ++i) {
+      const auto& a = c.arrays[i];
+      if (a.zc || !a.write || !a.write_all || !owns(i)) continue;
+      wk.d2h(l.s, a, 0, a.bytes / a.elem_size);
+      down += a.bytes;
+    }
+  }
+  void close(Lane l, bool wait_for_it) {
+    if (cs.zc_release && !cs.enqueue_mode_ && writes_host_memory(c)) wk.system_release(l.s);
+    if (cs.fine_grained) {
+      if (cs.defer_marker)
+        wk.defer_marker(l.s, marker_needs_release(c));
+      else
+        wk.add_marker(l.s, marker_needs_release(c));
+    }
+    if (wait_for_it && wk.gpu()) wk.wait_stream(l.s, cs.sleep_waits || cs.sleep_this_call_);
+  }
+};
+
 void Cores::run_3phase(Worker& wk, int gidx, const ComputeCall& c, long long ref, long long range,
                        uint64_t* h2d, uint64_t* d2h) {
-  hipStream_t s = nullptr;
-  if (wk.gpu())
-    s = (enqueue_mode_ && async_enqueue) ? wk.compute_stream(wk.next_compute_queue()) : wk.main_stream();
+  Ordering o{*this, wk, gidx, c, *h2d, *d2h, /*logged=*/false};
+  const int w = wk.index();
+  Lane l = wk.main_lane();
+  if (wk.gpu() && enqueue_mode_ && async_enqueue) l = wk.compute_lane(wk.next_compute_queue());
+  hipStream_t s = l.s;
   const bool defer = defer_downloads(wk);
   if (!defer || must_flush_before(wk, s, c))
     flush_downloads(wk, s, &c);  // this compute runs after every earlier download
@@ -1290,30 +1366,23 @@ void Cores::run_3phase(Worker& wk, int gidx, const ComputeCall& c, long long ref
   };
   // phase 1: host → device (partial slice wins over full read; an array
   // with explicit blob slices, run without its pipeline, goes up whole)
-  for (auto& a : c.arrays) {
-    if (a.zc) continue;
-    if (a.partial) {
-      uint64_t b, n;
-      if (!a.blob_begin.empty()) {
-        b = 0;
-        n = a.bytes / a.elem_size;
-      } else {
-        a.slice(ref, range, c.local_range, b, n);
-      }
-      wk.h2d(s, a, b, n);
-      *h2d += n * a.elem_size;
+  o.h2d(l, ref, range, [&](const ArraySpec& a, uint64_t& b, uint64_t& n) {
+    if (!a.blob_begin.empty()) {
+      b = 0;
+      n = a.bytes / a.elem_size;
+    } else {
+      a.slice(ref, range, c.local_range, b, n);
     }
-  }
-  full_reads(wk, s, c, h2d);
+    return true;
+  });
+  o.full_reads(l);
   // the earlier computes' downloads go into the copy queues after this
   // compute's uploads
   if (defer) flush_downloads(wk);
   // phase 2: kernels
-  launch_kernels(wk, s, c, ref, range);
-  if (call_gathers_ && wk.gpu()) {  // in-process gather: this device's kernels are enqueued
-    const int w = worker_index(wk);
-    CEK_HIP(hipEventRecord(gather_event(kdone_, w), s));
-  }
+  o.kernels(l, ref, range);
+  // in-process gather: this device's kernels are enqueued
+  if (call_gathers_ && wk.gpu()) CEK_HIP(hipEventRecord(gather_event(kdone_, w), s));
   // optional device-side all-gather of written slices (distributed keep-resident)
   if (gather) {
     auto& st = state_[c.compute_id];
@@ -1334,7 +1403,7 @@ void Cores::run_3phase(Worker& wk, int gidx, const ComputeCall& c, long long ref
   // no device may write its slice into host memory another device is still
   // reading (reference: all reads and computes finish before any write).
   if (phase_) {
-    DevSpans* ds = wk.gpu() ? &spans_[worker_index(wk)] : nullptr;
+    DevSpans* ds = wk.gpu() ? &spans_[w] : nullptr;
     if (ds) {
       if (!ds->gap_a) {
         CEK_HIP(hipEventCreateWithFlags(&ds->gap_a, kTimingEventFlags));
@@ -1352,71 +1421,43 @@ void Cores::run_3phase(Worker& wk, int gidx, const ComputeCall& c, long long ref
       ds->gap = true;
     }
   }
-  // phase 3: device → host (deferred in async enqueue mode, see PendingD2H)
-  const int wi = defer ? worker_index(wk) : -1;
-  auto download = [&](const ArraySpec& a, uint64_t b, uint64_t n) {
-    if (wi >= 0)
-      pending_d2h_[wi].push_back({s, a, b, n});
-    else
-      wk.d2h(s, a, b, n);
-  };
+  // phase 3: device → host, in the arrays' order (deferred in async enqueue
+  // mode, see PendingD2H)
   bool deferred_any = false;
   for (size_t i = 0; i < c.arrays.size(); ++i) {
     const auto& a = c.arrays[i];
     if (a.zc || !a.write) continue;
-    deferred_any = wi >= 0;
-    if (a.write_all) {
-      if (static_cast<int>(i % global_devices_) == gidx) {
-        download(a, 0, a.bytes / a.elem_size);
-        *d2h += a.bytes;
-      }
-    } else if (gathered(a)) {  // the replica holds every rank's slice
-      download(a, 0, a.bytes / a.elem_size);
-      *d2h += a.bytes;
-    } else {
-      uint64_t b, n;
-      a.slice(ref, range, c.local_range, b, n);
-      download(a, b, n);
-      *d2h += n * a.elem_size;
-    }
+    deferred_any = defer;
+    if (a.write_all && !o.owns(i)) continue;
+    uint64_t b = 0, n = a.bytes / a.elem_size;  // an owner's whole array; a replica holding every rank's slice
+    if (!a.write_all && !gathered(a)) a.slice(ref, range, c.local_range, b, n);
+    if (defer)
+      pending_d2h_[w].push_back({s, a, b, n});
+    else
+      wk.d2h(s, a, b, n);
+    *d2h += n * a.elem_size;
   }
   if (deferred_any && wk.gpu() && spans_on()) {
     // the span closes after the deferred download too
-    const DevSpans& d = spans_[wi];
-    pending_span_end_[wi].push_back({s, d.used - 1});
+    pending_span_end_[w].push_back({s, spans_[w].used - 1});
   } else {
     span_end(wk, s);
   }
-  if (zc_release && !enqueue_mode_ && writes_host_memory(c)) wk.system_release(s);
-  if (fine_grained) {
-    if (defer_marker)
-      wk.defer_marker(s, marker_needs_release(c));
-    else
-      wk.add_marker(s, marker_needs_release(c));
-  }
-  if (!enqueue_mode_ && wk.gpu()) wk.wait_stream(s, sleep_waits || sleep_this_call_);
+  o.close(l, !enqueue_mode_);
 }
 
 void Cores::run_event_pipeline(Worker& wk, int gidx, const ComputeCall& c, long long ref,
                                long long range, uint64_t* h2d, uint64_t* d2h) {
+  Ordering o{*this, wk, gidx, c, *h2d, *d2h, /*logged=*/true};
   const long long B = std::max(1, c.blobs);
   const long long chunk = range / B;
   const int halves = (B % 2 == 0) ? 2 : 1;
   const long long per_half = B / halves;
-  hipStream_t m = wk.main_stream();
-  span_begin(wk, m);
-  full_reads(wk, m, c, h2d);
-  log_op(gidx, "h2d", 0, -1, -1);  // full reads
-  int slot = 0;
-  hipEvent_t ev_full = nullptr;
-  if (wk.gpu()) {
-    ev_full = wk.event(slot);
-    CEK_HIP(hipEventRecord(ev_full, m));
-    for (int h = 0; h < halves; ++h) CEK_HIP(hipStreamWaitEvent(wk.pipe_stream(h, 1), ev_full, 0));
-  }
-  log_op(gidx, "rec", 0, 0, 0, slot);
-  for (int h = 0; h < halves; ++h) log_op(gidx, "wait", 17 + 3 * h + 1, 0, 0, slot);
-  ++slot;
+  const Lane m = wk.main_lane();
+  span_begin(wk, m.s);
+  o.full_reads(m);
+  const int full = o.mark(m, 0, 0);
+  for (int h = 0; h < halves; ++h) o.wait(wk.pipe_lane(h, 1), full, 0, 0);
   // Interleave the two half-pipelines' chunks so both read streams start
   // early; explicit blobs (c.blob_bounds) alternate between the halves.
   const bool explicit_blobs = !c.blob_bounds.empty();
@@ -1429,251 +1470,104 @@ void Cores::run_event_pipeline(Worker& wk, int gidx, const ComputeCall& c, long 
   // 4.72 ms for 256 MiB); inside the shell pipeline the extra stream shares
   // a hardware queue with kernel and download streams and the call slows
   // from 7.1 to 12.7 ms (profiles/round4_session4.md), so it stays off.
-  const bool two_reads = explicit_blobs && pipeline_reads_on_main_stream && pipeline_reads_two_streams;
-  hipStream_t rs2 = nullptr;
-  const int rs2id = 17;  // pipe_stream(0, 0), as logged for the schedule checker
-  if (two_reads) {
-    if (wk.gpu()) {
-      rs2 = wk.pipe_stream(0, 0);
-      CEK_HIP(hipStreamWaitEvent(rs2, ev_full, 0));
-    }
-    log_op(gidx, "wait", rs2id, 0, 0, 0);
-  }
+  const int nread = (explicit_blobs && pipeline_reads_on_main_stream && pipeline_reads_two_streams) ? 2 : 1;
+  const Lane rs2 = nread == 2 ? wk.pipe_lane(0, 0) : Lane{};
+  if (nread == 2) o.wait(rs2, full, 0, 0);
   for (long long q = 0; q < nblob; ++q) {
-    {
-      const long long k = explicit_blobs ? q : q / halves;
-      const int h = explicit_blobs ? static_cast<int>(q % 2) : static_cast<int>(q % halves);
-      // reads_on_main_stream: every blob's upload follows the full reads on
-      // the main stream (one in-order chain of copies).  Explicit blobs always
-      // upload there: blob q's kernels may read panels uploaded by earlier
-      // blobs of the OTHER half (shell s reads panels 0..s), which only one
-      // in-order upload chain orders before them
-      const bool reads_main = pipeline_reads_on_main_stream || explicit_blobs;
-      hipStream_t rs = reads_main ? m : wk.pipe_stream(h, 0), ks = wk.pipe_stream(h, 1);
-      // writes_on_compute_stream: a blob's D2H follows its kernel on the same
-      // stream (in-stream order) instead of a write stream gated by an event
-      hipStream_t ws = pipeline_writes_on_compute_stream ? ks : wk.pipe_stream(pipeline_writes_one_stream ? 0 : h, 2);
-      const long long off = explicit_blobs ? ref + c.blob_bounds[q] : ref + h * (range / halves) + k * chunk;
-      const long long len = explicit_blobs ? c.blob_bounds[q + 1] - c.blob_bounds[q] : chunk;
-      const int ksid = 17 + 3 * h + 1;
-      const int wsid = pipeline_writes_on_compute_stream ? ksid : (pipeline_writes_one_stream ? 19 : ksid + 1);
-      const int rsid = reads_main ? 0 : ksid - 1;  // as logged for the schedule checker
-      auto blob_slice = [&](const ArraySpec& a, uint64_t& b, uint64_t& n) {
-        if (explicit_blobs && a.blob_begin.size() == c.blob_bounds.size() - 1) {
-          b = a.blob_begin[q];
-          n = a.blob_count[q];
-        } else {
-          a.slice(off, len, c.local_range, b, n);
-        }
-      };
+    const long long k = explicit_blobs ? q : q / halves;
+    const int h = explicit_blobs ? static_cast<int>(q % 2) : static_cast<int>(q % halves);
+    // reads_on_main_stream: every blob's upload follows the full reads on
+    // the main stream (one in-order chain of copies).  Explicit blobs always
+    // upload there: blob q's kernels may read panels uploaded by earlier
+    // blobs of the OTHER half (shell s reads panels 0..s), which only one
+    // in-order upload chain orders before them
+    const bool reads_main = pipeline_reads_on_main_stream || explicit_blobs;
+    const Lane rs = reads_main ? m : wk.pipe_lane(h, 0), ks = wk.pipe_lane(h, 1);
+    // writes_on_compute_stream: a blob's D2H follows its kernel on the same
+    // stream (in-stream order) instead of a write stream gated by an event
+    const Lane ws = pipeline_writes_on_compute_stream ? ks : wk.pipe_lane(pipeline_writes_one_stream ? 0 : h, 2);
+    const long long off = explicit_blobs ? ref + c.blob_bounds[q] : ref + h * (range / halves) + k * chunk;
+    const long long len = explicit_blobs ? c.blob_bounds[q + 1] - c.blob_bounds[q] : chunk;
+    auto blob_slice = [&](const ArraySpec& a, uint64_t& b, uint64_t& n) {
+      if (explicit_blobs && a.blob_begin.size() == c.blob_bounds.size() - 1) {
+        b = a.blob_begin[q];
+        n = a.blob_count[q];
+      } else {
+        a.slice(off, len, c.local_range, b, n);
+      }
+      return true;
+    };
+    // with two upload streams the partial arrays alternate between them, and
+    // every blob's kernels wait for both, also a blob that uploads nothing
+    // on the second (its kernels may need an earlier blob's panel, and
+    // consecutive blobs' kernels run on different streams)
+    for (int j = 0; j < nread; ++j) {
+      const Lane r = j ? rs2 : rs;
       int pi = 0;
-      for (auto& a : c.arrays) {
-        if (a.zc || !a.partial) continue;
-        uint64_t b, n;
-        blob_slice(a, b, n);
-        const bool on2 = two_reads && (pi++ % 2 == 1);
-        wk.h2d(on2 ? rs2 : rs, a, b, n);
-        *h2d += n * a.elem_size;
-      }
-      log_op(gidx, "h2d", rsid, off, len);
-      if (wk.gpu()) {
-        hipEvent_t er = wk.event(slot);
-        CEK_HIP(hipEventRecord(er, rs));
-        CEK_HIP(hipStreamWaitEvent(ks, er, 0));
-      }
-      log_op(gidx, "rec", rsid, off, len, slot);
-      log_op(gidx, "wait", ksid, off, len, slot);
-      ++slot;
-      if (two_reads) {
-        // every blob's kernels wait for the second stream too, also a blob
-        // that uploads nothing there (its kernels may need an earlier blob's
-        // panel, and consecutive blobs' kernels run on different streams)
-        log_op(gidx, "h2d", rs2id, off, len);
-        if (wk.gpu()) {
-          hipEvent_t er2 = wk.event(slot);
-          CEK_HIP(hipEventRecord(er2, rs2));
-          CEK_HIP(hipStreamWaitEvent(ks, er2, 0));
-        }
-        log_op(gidx, "rec", rs2id, off, len, slot);
-        log_op(gidx, "wait", ksid, off, len, slot);
-        ++slot;
-      }
-      launch_kernels(wk, ks, c, off, len);
-      log_op(gidx, "kernel", ksid, off, len);
-      if (wk.gpu() && ws != ks) {
-        hipEvent_t ek = wk.event(slot);
-        CEK_HIP(hipEventRecord(ek, ks));
-        CEK_HIP(hipStreamWaitEvent(ws, ek, 0));
-      }
-      log_op(gidx, "rec", ksid, off, len, slot);
-      log_op(gidx, "wait", wsid, off, len, slot);
-      ++slot;
-      for (auto& a : c.arrays) {
-        if (a.zc || !a.write || a.write_all) continue;
-        uint64_t b, n;
-        blob_slice(a, b, n);
-        wk.d2h(ws, a, b, n);
-        *d2h += n * a.elem_size;
-      }
-      log_op(gidx, "d2h", wsid, off, len);
+      o.h2d(r, off, len, [&](const ArraySpec& a, uint64_t& b, uint64_t& n) {
+        return pi++ % nread == j && blob_slice(a, b, n);
+      });
+      o.link(r, ks, off, len);
     }
+    o.kernels(ks, off, len);
+    o.link(ks, ws, off, len);
+    o.d2h(ws, off, len, blob_slice);
   }
   // write-all owners download after every chunk's kernels
-  bool any_all = false;
-  for (auto& a : c.arrays) any_all |= (a.write && a.write_all && !a.zc);
   for (int h = 0; h < used_halves; ++h) {
-    if (wk.gpu()) {
-      hipEvent_t e = wk.event(slot);
-      CEK_HIP(hipEventRecord(e, wk.pipe_stream(h, 1)));
-      CEK_HIP(hipStreamWaitEvent(m, e, 0));
-      hipEvent_t e2 = wk.event(slot + 1);
-      CEK_HIP(hipEventRecord(e2, wk.pipe_stream(h, 2)));
-      CEK_HIP(hipStreamWaitEvent(m, e2, 0));
-    }
-    log_op(gidx, "rec", 17 + 3 * h + 1, 0, 0, slot);
-    log_op(gidx, "wait", 0, 0, 0, slot);
-    log_op(gidx, "rec", 17 + 3 * h + 2, 0, 0, slot + 1);
-    log_op(gidx, "wait", 0, 0, 0, slot + 1);
-    slot += 2;
+    o.link(wk.pipe_lane(h, 1), m, 0, 0);
+    o.link(wk.pipe_lane(h, 2), m, 0, 0);
   }
-  if (any_all) {
-    for (size_t i = 0; i < c.arrays.size(); ++i) {
-      const auto& a = c.arrays[i];
-      if (a.write && a.write_all && !a.zc && static_cast<int>(i % global_devices_) == gidx) {
-        wk.d2h(m, a, 0, a.bytes / a.elem_size);
-        *d2h += a.bytes;
-      }
-    }
-  }
-  span_end(wk, m);
-  if (zc_release && !enqueue_mode_ && writes_host_memory(c)) wk.system_release(m);
-  if (fine_grained) {
-    if (defer_marker)
-      wk.defer_marker(m, marker_needs_release(c));
-    else
-      wk.add_marker(m, marker_needs_release(c));
-  }
-  if (wk.gpu()) wk.wait_stream(m, sleep_waits || sleep_this_call_);
+  o.write_all_downloads(m);
+  span_end(wk, m.s);
+  o.close(m, true);
 }
 
 void Cores::run_driver_pipeline(Worker& wk, int gidx, const ComputeCall& c, long long ref,
                                 long long range, uint64_t* h2d, uint64_t* d2h) {
+  Ordering o{*this, wk, gidx, c, *h2d, *d2h, /*logged=*/true};
   const long long B = std::max(1, c.blobs);
   const long long chunk = range / B;
-  hipStream_t m = wk.main_stream();
-  span_begin(wk, m);
-  full_reads(wk, m, c, h2d);
-  log_op(gidx, "h2d", 0, -1, -1);  // full reads
-  int slot = 0;
-  hipEvent_t ev_full = nullptr;
-  if (wk.gpu()) {
-    ev_full = wk.event(slot);
-    CEK_HIP(hipEventRecord(ev_full, m));
-  }
-  log_op(gidx, "rec", 0, 0, 0, slot);
-  const int full_slot = slot++;
+  const Lane m = wk.main_lane();
+  span_begin(wk, m.s);
+  o.full_reads(m);
+  const int full = o.mark(m, 0, 0);  // each queue waits for it at its first blob
   const int nq = wk.queue_concurrency();
-  std::vector<char> used(16, 0);
-  // the download stream (the event pipeline's first write stream, id 19 in
-  // the schedule log)
-  const bool own_dl = driver_downloads_own_stream;
-  hipStream_t ds = own_dl && wk.gpu() ? wk.pipe_stream(0, 2) : nullptr;
-  const int dsid = 19;
-  bool ds_used = false;
+  bool used[16] = {};
+  auto is_read = [](const ArraySpec& a) { return !a.zc && a.partial; };
+  auto is_written = [](const ArraySpec& a) { return !a.zc && a.write && !a.write_all; };
+  // reads_main: a blob's upload goes into the main stream's one in-order
+  // chain of copies and its queue waits for it, so no upload waits behind
+  // an earlier blob's kernel in a compute queue
+  const bool reads_main = driver_reads_on_main_stream && wk.gpu();
+  const bool link_reads = reads_main && std::any_of(c.arrays.begin(), c.arrays.end(), is_read);
+  // the blobs' downloads go to one download stream (the event pipeline's
+  // first write stream)
+  const bool own_dl = driver_downloads_own_stream && wk.gpu() &&
+                      std::any_of(c.arrays.begin(), c.arrays.end(), is_written);
+  const Lane dl = driver_downloads_own_stream && wk.gpu() ? wk.pipe_lane(0, 2) : Lane{};
   for (long long k = 0; k < B; ++k) {
-    int qi = static_cast<int>(k % nq);
-    hipStream_t s = wk.compute_stream(qi);
-    if (!used[qi]) {
-      if (wk.gpu()) CEK_HIP(hipStreamWaitEvent(s, ev_full, 0));
-      log_op(gidx, "wait", 1 + qi, 0, 0, full_slot);
-    }
-    used[qi] = 1;
-    long long off = ref + k * chunk;
-    // reads_main: the blob's upload goes into the main stream's one in-order
-    // chain of copies and its queue waits for it, so no upload waits behind
-    // an earlier blob's kernel in a compute queue
-    const bool reads_main = driver_reads_on_main_stream && wk.gpu();
-    hipStream_t rs = reads_main ? m : s;
-    bool reads = false;
-    for (auto& a : c.arrays) {
-      if (a.zc || !a.partial) continue;
-      uint64_t b, n;
+    const int qi = static_cast<int>(k % nq);
+    const Lane q = wk.compute_lane(qi);
+    if (!used[qi]) o.wait(q, full, 0, 0);
+    used[qi] = true;
+    const long long off = ref + k * chunk;
+    auto items = [&](const ArraySpec& a, uint64_t& b, uint64_t& n) {
       a.slice(off, chunk, c.local_range, b, n);
-      wk.h2d(rs, a, b, n);
-      *h2d += n * a.elem_size;
-      reads = true;
-    }
-    log_op(gidx, "h2d", reads_main ? 0 : 1 + qi, off, chunk);
-    if (reads_main && reads) {
-      hipEvent_t er = wk.event(slot);
-      CEK_HIP(hipEventRecord(er, m));
-      CEK_HIP(hipStreamWaitEvent(s, er, 0));
-      log_op(gidx, "rec", 0, off, chunk, slot);
-      log_op(gidx, "wait", 1 + qi, off, chunk, slot);
-      ++slot;
-    }
-    launch_kernels(wk, s, c, off, chunk);
-    log_op(gidx, "kernel", 1 + qi, off, chunk);
-    bool writes = false;
-    for (auto& a : c.arrays) writes |= !a.zc && a.write && !a.write_all;
-    hipStream_t w = s;
-    const bool to_ds = own_dl && writes && wk.gpu();
-    if (to_ds) {
-      hipEvent_t ek = wk.event(slot);
-      CEK_HIP(hipEventRecord(ek, s));
-      CEK_HIP(hipStreamWaitEvent(ds, ek, 0));
-      w = ds;
-      log_op(gidx, "rec", 1 + qi, off, chunk, slot);
-      log_op(gidx, "wait", dsid, off, chunk, slot);
-      ++slot;
-      ds_used = true;
-    }
-    for (auto& a : c.arrays) {
-      if (a.zc || !a.write || a.write_all) continue;
-      uint64_t b, n;
-      a.slice(off, chunk, c.local_range, b, n);
-      wk.d2h(w, a, b, n);
-      *d2h += n * a.elem_size;
-    }
-    log_op(gidx, "d2h", to_ds ? dsid : 1 + qi, off, chunk);
+      return true;
+    };
+    o.h2d(reads_main ? m : q, off, chunk, items);
+    if (link_reads) o.link(m, q, off, chunk);
+    o.kernels(q, off, chunk);
+    if (own_dl) o.link(q, dl, off, chunk);
+    o.d2h(own_dl ? dl : q, off, chunk, items);
   }
-  if (ds_used) {  // the call ends after the last download
-    if (wk.gpu()) {
-      hipEvent_t e = wk.event(slot);
-      CEK_HIP(hipEventRecord(e, ds));
-      CEK_HIP(hipStreamWaitEvent(m, e, 0));
-    }
-    log_op(gidx, "rec", dsid, 0, 0, slot);
-    log_op(gidx, "wait", 0, 0, 0, slot);
-    ++slot;
-  }
-  for (int q = 0; q < 16; ++q) {
-    if (!used[q]) continue;
-    if (wk.gpu()) {
-      hipEvent_t e = wk.event(slot);
-      CEK_HIP(hipEventRecord(e, wk.compute_stream(q)));
-      CEK_HIP(hipStreamWaitEvent(m, e, 0));
-    }
-    log_op(gidx, "rec", 1 + q, 0, 0, slot);
-    log_op(gidx, "wait", 0, 0, 0, slot);
-    ++slot;
-  }
-  for (size_t i = 0; i < c.arrays.size(); ++i) {
-    const auto& a = c.arrays[i];
-    if (a.write && a.write_all && !a.zc && static_cast<int>(i % global_devices_) == gidx) {
-      wk.d2h(m, a, 0, a.bytes / a.elem_size);
-      *d2h += a.bytes;
-    }
-  }
-  span_end(wk, m);
-  if (zc_release && !enqueue_mode_ && writes_host_memory(c)) wk.system_release(m);
-  if (fine_grained) {
-    if (defer_marker)
-      wk.defer_marker(m, marker_needs_release(c));
-    else
-      wk.add_marker(m, marker_needs_release(c));
-  }
-  if (wk.gpu()) wk.wait_stream(m, sleep_waits || sleep_this_call_);
+  if (own_dl) o.link(dl, m, 0, 0);  // the call ends after the last download
+  for (int q = 0; q < 16; ++q)
+    if (used[q]) o.link(wk.compute_lane(q), m, 0, 0);
+  o.write_all_downloads(m);
+  span_end(wk, m.s);
+  o.close(m, true);
 }
 
 void Cores::run_device(int w, const ComputeCall& c, long long ref, long long range, bool pipelined,

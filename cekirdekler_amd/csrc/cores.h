@@ -200,9 +200,10 @@ class Cores {
   bool auto_failover = false;
   // ---- schedule recording (pipeline dependency checks) ----
   // Every transfer / kernel / event edge the pipelines issue is appended as
-  // (device, op, logical stream, first work item, work items, event).
-  // Logical streams: 0 main, 1+k compute queue k, 17+3h+r pipeline half h
-  // role r (0 read, 1 compute, 2 write).
+  // (device, op, logical stream, first work item, work items, event), by the
+  // call that issues it (Cores::Ordering, cores.cpp).  The logical stream is
+  // the id of the Lane it ran on (worker.h: main_lane_id, compute_lane_id,
+  // pipe_lane_id).
   struct SchedOp {
     int device;
     std::string op;  // h2d | kernel | d2h | rec | wait
@@ -363,6 +364,8 @@ class Cores {
   // some processes stayed at 14 ms per streamed GEMM call instead of 8
   // (profiles/hostres_streaming.md, tools/hostres_stall_probe.py)
   bool pipeline_reads_on_main_stream = true;
+  // explicit blobs: partial arrays alternate over two upload streams (slower:
+  // 12.7 vs 7.1 ms for the shells, the extra stream shares a hardware queue)
   bool pipeline_reads_two_streams = false;
   // driver pipeline (Cores.cs:1368-1858): blob k's upload and kernels stay on
   // queue k mod Q, its download goes to one download stream gated by the
@@ -384,7 +387,7 @@ class Cores {
   double sleep_wait_min_ms = 0.25;
   // GPU workers wait for their streams by sleeping on a blocking-sync event
   // (off by default; CEK_SLEEP_WAITS=1)
-  bool sleep_waits = false;  // explicit blobs: partial arrays alternate over two upload streams (slower: 12.7 vs 7.1 ms for the shells, the extra stream shares a hardware queue)
+  bool sleep_waits = false;
   uint64_t peer_read_min_bytes = 1u << 20;
 
  private:
@@ -394,6 +397,7 @@ class Cores {
                   double* out_ms, uint64_t* h2d, uint64_t* d2h);
   void run_device_body(int w, const ComputeCall& c, long long ref, long long range, bool pipelined,
                   double* out_ms, uint64_t* h2d, uint64_t* d2h);
+  struct Ordering;  // issues and logs what the three run_* shapes enqueue (cores.cpp)
   void run_3phase(Worker& wk, int gidx, const ComputeCall& c, long long ref, long long range,
                   uint64_t* h2d, uint64_t* d2h);
   void run_event_pipeline(Worker& wk, int gidx, const ComputeCall& c, long long ref,
@@ -424,7 +428,6 @@ class Cores {
   std::vector<char> staged_dev_;  // by local worker, for the current call
   uint64_t stage_peer_reads(const ComputeCall& c, const std::vector<long long>& ranges,
                             std::vector<uint64_t>& h2d);
-  int worker_index(const Worker& wk) const;
   // peer topology
   std::vector<int> peer_ordinals_;
   std::vector<std::vector<int>> peer_matrix_;

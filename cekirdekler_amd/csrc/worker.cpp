@@ -150,9 +150,9 @@ void CpuPool::parallel_for(long long n, const std::function<void(long long)>& fn
 
 // ------------------------------------------------------------------ Worker --
 
-Worker::Worker(const DeviceInfo& dev, std::shared_ptr<Program> prog, int queue_concurrency,
+Worker::Worker(const DeviceInfo& dev, std::shared_ptr<Program> prog, int index, int queue_concurrency,
                bool no_pipelining, int cpu_slot)
-    : dev_(dev), prog_(std::move(prog)), qconc_(queue_concurrency < 1 ? 1 : (queue_concurrency > 16 ? 16 : queue_concurrency)),
+    : dev_(dev), prog_(std::move(prog)), index_(index), qconc_(queue_concurrency < 1 ? 1 : (queue_concurrency > 16 ? 16 : queue_concurrency)),
       no_pipelining_(no_pipelining) {
   cq_.assign(16, nullptr);
   marker_issued_per_slot_.assign(32, 0);
@@ -549,13 +549,13 @@ void Worker::launch_graph(hipStream_t s, const std::string& key,
 }
 
 int Worker::stream_slot(hipStream_t s) {
-  if (s == main_) return 0;
+  if (s == main_) return main_lane_id();
   for (int i = 0; i < 16; ++i)
-    if (cq_[i] == s) return 1 + i;
+    if (cq_[i] == s) return compute_lane_id(i);
   for (int h = 0; h < 2; ++h)
     for (int r = 0; r < 3; ++r)
-      if (pq_[h][r] == s) return 17 + h * 3 + r;
-  return 31;
+      if (pq_[h][r] == s) return pipe_lane_id(h, r);
+  return kNoLane;
 }
 
 void Worker::h2d(hipStream_t s, const ArraySpec& a, uint64_t elem_begin, uint64_t elem_count) {
@@ -799,9 +799,10 @@ int Worker::device_enqueue_errors() {
 }
 
 hipStream_t Worker::slot_stream(int slot) const {
-  if (slot == 0) return main_;
-  if (slot >= 1 && slot <= 16) return cq_[slot - 1];
-  if (slot >= 17 && slot < 23) return pq_[(slot - 17) / 3][(slot - 17) % 3];
+  if (slot == main_lane_id()) return main_;
+  if (slot >= compute_lane_id(0) && slot < pipe_lane_id(0, 0)) return cq_[slot - compute_lane_id(0)];
+  if (slot >= pipe_lane_id(0, 0) && slot < pipe_lane_id(2, 0))
+    return pq_[(slot - pipe_lane_id(0, 0)) / 3][(slot - pipe_lane_id(0, 0)) % 3];
   return nullptr;
 }
 
@@ -811,7 +812,7 @@ void Worker::defer_marker(hipStream_t s, bool release) {
     return;
   }
   const int slot = stream_slot(s);
-  if (slot >= 31 || !slot_stream(slot)) {  // not a slot flush_markers() can find again
+  if (slot >= kNoLane || !slot_stream(slot)) {  // not a slot flush_markers() can find again
     add_marker(s, release);
     return;
   }
@@ -822,7 +823,7 @@ void Worker::defer_marker(hipStream_t s, bool release) {
 }
 
 void Worker::flush_markers() {
-  for (int slot = 0; deferred_slots_ != 0 && slot < 31; ++slot)
+  for (int slot = 0; deferred_slots_ != 0 && slot < kNoLane; ++slot)
     if (deferred_slots_ & (1u << slot)) add_marker(slot_stream(slot), false);
 }
 
@@ -834,7 +835,7 @@ void Worker::add_marker(hipStream_t s, bool release) {
     return;
   }
   int slot = stream_slot(s);
-  if (slot < 31 && (deferred_slots_ & (1u << slot))) {
+  if (slot < kNoLane && (deferred_slots_ & (1u << slot))) {
     // this marker also completes the computes deferred on the same stream
     release = release || (deferred_release_ & (1u << slot));
     deferred_slots_ &= ~(1u << slot);

@@ -102,15 +102,30 @@ class CpuPool {
 // How host threads wait for GPU `ordinal` (env CEK_HIP_SYNC, worker.cpp).
 void apply_sync_mode(int ordinal);
 
+// A stream together with its logical id.  The ids are the `stream` column of
+// the schedule log (Cores::SchedOp) and the worker's marker / join slots; this
+// is their one definition.  A CPU device's lanes have s == nullptr and the
+// same ids as a GPU's.
+struct Lane {
+  hipStream_t s;
+  int id;
+};
+constexpr int main_lane_id() { return 0; }
+constexpr int compute_lane_id(int q) { return 1 + q; }                    // q in [0, 16)
+constexpr int pipe_lane_id(int half, int role) { return 17 + 3 * half + role; }  // role 0=read 1=compute 2=write
+constexpr int kNoLane = 31;  // a stream that is none of the worker's
+
 class Worker {
  public:
+  // index: this worker's place among its Cores' workers
   // cpu_slot: this CPU device's index among the CPU devices of its set
   // (CpuPool::shared); ignored for a GPU
-  Worker(const DeviceInfo& dev, std::shared_ptr<Program> prog, int queue_concurrency,
+  Worker(const DeviceInfo& dev, std::shared_ptr<Program> prog, int index, int queue_concurrency,
          bool no_pipelining, int cpu_slot = 0);
   ~Worker();
 
   const DeviceInfo& dev() const { return dev_; }
+  int index() const { return index_; }
   bool gpu() const { return dev_.type == kGPU; }
   uintptr_t cpu_pool_id() const { return reinterpret_cast<uintptr_t>(pool_.get()); }
   Program& program() { return *prog_; }
@@ -129,6 +144,11 @@ class Worker {
   hipStream_t main_stream();
   hipStream_t compute_stream(int i);        // i in [0, queue_concurrency)
   hipStream_t pipe_stream(int half, int role);  // role 0=read 1=compute 2=write
+  // the same streams with their logical ids; compute_lane(q).id stays 1 + q
+  // when one queue (queue_concurrency 1) aliases the stream to main
+  Lane main_lane() { return {main_stream(), main_lane_id()}; }
+  Lane compute_lane(int q) { return {compute_stream(q), compute_lane_id(q)}; }
+  Lane pipe_lane(int half, int role) { return {pipe_stream(half, role), pipe_lane_id(half, role)}; }
   // Reserve `n` CUs (spread evenly over the XCDs) for copy kernels: the
   // pipeline's write streams run on those CUs only and every other stream
   // on the rest (hipExtStreamCreateWithCUMask).  A download by copy kernel
@@ -239,6 +259,7 @@ class Worker {
 
   DeviceInfo dev_;
   std::shared_ptr<Program> prog_;
+  int index_;
   int qconc_;
   bool no_pipelining_;
   unsigned dyn_lds_ = 0;
