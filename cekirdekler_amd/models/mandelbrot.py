@@ -89,16 +89,17 @@ class MandelbrotRenderer:
         self.out.elements_per_work_item = self.ppw
         self.global_range = width * height // self.ppw
         self._last_id = None
-        self._uploaded = set()  # (compute id, view bytes, size bytes) already on the devices
+        self._uploaded = None  # (view bytes, size bytes) that every local device holds
 
     def render(self, compute_id: int = 1, pipeline: bool = True, blobs: int = 8,
                pipeline_type: bool = PIPELINE_EVENT) -> np.ndarray:
-        # The view and size parameters go up only when they changed since
-        # this compute id last ran (two 16-byte copies on the main stream
-        # would delay the first blob's kernel, and with it the first D2H,
-        # by their latency).
-        params = (compute_id, self.view.array.tobytes(), self.size.array.tobytes())
-        fresh = params not in self._uploaded
+        # The view and size parameters go up only when they differ from what
+        # the devices hold (two 16-byte copies on the main stream would delay
+        # the first blob's kernel, and with it the first D2H, by their
+        # latency).  A device holds one copy per array, whatever the compute
+        # id, so only the last upload counts.
+        params = (self.view.array.tobytes(), self.size.array.tobytes())
+        fresh = params != self._uploaded
         self.view.read = self.size.read = fresh
         self.view.next_param(self.size, self.out).compute(
             self.cr, compute_id, self.kernel, self.global_range, self.local, 0, pipeline,
@@ -106,8 +107,8 @@ class MandelbrotRenderer:
         self._last_id = compute_id
         if fresh:
             base, n = self.cr._cores.global_base, self.cr._cores.num_devices
-            if all(r > 0 for r in self.cr.ranges(compute_id)[base:base + n]):
-                self._uploaded.add(params)  # every local device holds them now
+            every = all(r > 0 for r in self.cr.ranges(compute_id)[base:base + n])
+            self._uploaded = params if every else None  # a device left out still holds the old ones
         return self.out.array.reshape(self.height, self.width)
 
     def local_slice(self) -> slice:
