@@ -100,18 +100,25 @@ def _file_flags(src: str) -> list[str]:
     return flags
 
 
-def build_kernels(force: bool = False, jobs: int = 8) -> list[str]:
+def hipcc_path() -> str:
     hipcc = os.path.join(ROCM, "bin", "hipcc")
-    if not os.path.exists(hipcc):
-        hipcc = shutil.which("hipcc") or "hipcc"
+    return hipcc if os.path.exists(hipcc) else shutil.which("hipcc") or "hipcc"
+
+
+def kernel_command(src: str, out: str) -> list[str]:
+    """The one command line a library kernel file is compiled with."""
+    return [hipcc_path(), "--genco", f"--offload-arch={ARCH}", "-O3", "-std=c++17",
+            "-mcode-object-version=5", f"-I{os.path.dirname(src)}", *_file_flags(src), src, "-o", out]
+
+
+def build_kernels(force: bool = False, jobs: int = 8) -> list[str]:
     todo, outs = [], []
     inc_hdrs = [os.path.join(KDIR, f) for f in os.listdir(KDIR) if f.endswith(".h")] if os.path.isdir(KDIR) else []
     for src in kernel_sources():
         out = src[:-4] + ".hsaco"
         outs.append(out)
         if force or not _newer(out, [src] + inc_hdrs):
-            todo.append([hipcc, "--genco", f"--offload-arch={ARCH}", "-O3", "-std=c++17",
-                         "-mcode-object-version=5", f"-I{KDIR}", *_file_flags(src), src, "-o", out])
+            todo.append(kernel_command(src, out))
     if todo:
         with cf.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
             list(ex.map(_run, todo))

@@ -22,13 +22,8 @@
 // 16-B chunk index is XOR-swizzled with (row & 7) on the global SOURCE
 // address and on the ds_read_b128 address (rule 21), which makes every
 // fragment read conflict-free (each 16-lane group hits 16 distinct slots).
-#include "cek_kernel.h"
+#include "gemm_parts.h"
 
-// K-tile index of a stage load; tools/microbench/gemm_loop.hip redefines it
-// to re-read two K-tiles (an L2-resident operand stream) as a probe.
-#ifndef CEK_KTILE
-#define CEK_KTILE(ks, kt) ((ks) + (kt))
-#endif
 // Per-work-group timeline stamps (tools/microbench/gemm_loop.hip defines it
 // in its timeline build; empty in the library).
 #ifndef CEK_TS
@@ -37,12 +32,24 @@
 
 namespace {
 
+// LDS bytes of a tile.  MODE 0 / 2: two whole stages (A rows, then Bt rows).
+// MODE 4: two A buffers and three Bt buffers.  MODE 6: three whole stages.
+constexpr int gemm_lds_bytes(int WM, int WN, int FM, int FN, int MODE) {
+  const int a = WM * 16 * FM * 64 * 2, b = WN * 16 * FN * 64 * 2;
+  return MODE == 4 ? 2 * a + 3 * b : MODE == 6 ? 3 * (a + b) : 2 * (a + b);
+}
+
+// The parts below are lambdas that capture by reference, and the shared
+// helpers take their operands by reference: written so, the device code is
+// byte-identical to the one-function-per-variant text this replaced
+// (tools/kernel_identity.py).
 template <int WM, int WN, int FM, int FN, int MODE, bool SK = false, int XCH = 0, bool ROWC = false>
 __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
                                           const uint16_t* __restrict__ A,
                                           const uint16_t* __restrict__ Bt, float* __restrict__ C,
                                           char* smem, long long off, float* __restrict__ W = nullptr,
                                           int* __restrict__ tile_cnt = nullptr) {
+  static_assert(MODE == 0 || MODE == 2 || MODE == 4 || MODE == 6, "MODE is 0, 2, 4 or 6");
   constexpr int BM = WM * 16 * FM, BN = WN * 16 * FN, BK = 64;
   constexpr int NREG = WM * WN;
   constexpr int NWAVES = NREG, NT = 64 * NWAVES;
@@ -58,6 +65,7 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
   constexpr int A_INSTR = A_BYTES / 1024 / STAGERS;
   constexpr int B_INSTR = B_BYTES / 1024 / STAGERS;
 
+  // ---- prologue: who am I, which tile, which K-tiles ----
   const int M = dims[0], N = dims[1], K = dims[2], GM = dims[3] > 0 ? dims[3] : 1;
   const int tid = threadIdx.x, lane = tid & 63;
   CEK_TS(0);
@@ -80,48 +88,51 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
   // t, so a device's contiguous tile range is still one contiguous slice.
   const int ntn = N / BN, ntm = M / BM;
   int tm, tn;
-  // a launch wider than the tile grid (a host-side range error) must not
-  // read or write past A, B or C: surplus work-groups leave at once
-  if (t >= (long long)ntm * ntn) return;
-  cek_tile_coords(t, ntm, ntn, GM, dims[6], tm, tn);
+  if (!cek_tile_lookup(dims, GM, t, ntm, ntn, tm, tn)) return;
   const int m0 = tm * BM, n0 = tn * BN;
 
-  // Staging: instruction `ins` of this wave fills LDS bytes [ins·1 KiB, +1 KiB)
-  // = 8 rows × 128 B; lane l lands at row ins·8 + l/8, physical chunk l%8,
-  // which holds logical chunk (l%8) ^ (row & 7).
-  // Within one wave-instruction the 8 rows are ins·8 .. ins·8+7, so the
-  // logical chunk (l%8) ^ (row&7) = (l%8) ^ (l/8) is the same for every
-  // instruction: one per-lane base pointer plus a uniform row stride.
-  const int lrow = lane >> 3, lchunk = (lane & 7) ^ (lrow & 7);
-  // per-lane 32-bit byte offset + wave-uniform 64-bit base (saddr form)
-  const unsigned lane_off = (unsigned)(lrow * K + lchunk * 8) * 2u;
+  // ---- staging (geometry: gemm_parts.h) ----
+  const unsigned lane_off = cek_stage_lane_off<2>(lane, K);
   const int sw = MODE >= 2 ? wave % (NWAVES / 2) : wave;  // staging wave index
   const char* a_wave = (const char*)(A + (size_t)(m0 + sw * A_INSTR * 8) * K);
   const char* b_wave = (const char*)(Bt + (size_t)(n0 + sw * B_INSTR * 8) * K);
-
+  // this wave's share of K-tile kt's A (Bt) rows into whole stage `buf` (A
+  // rows, then Bt rows): MODE 0 / 2 and the hand-over fall-back
   auto stage_a = [&](int buf, int kt) {
-    char* base = smem + buf * STAGE;
-#pragma unroll
-    for (int j = 0; j < A_INSTR; ++j) {
-      const char* src = a_wave + ((size_t)j * 8 * K + (size_t)CEK_KTILE(ks, kt) * BK) * 2;
-      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                       (lds_void*)(base + (sw * A_INSTR + j) * 1024), 16, 0, 0);
-    }
+    cek_stage_rows<A_INSTR, 2>(a_wave, lane_off, K, ks, kt, smem + buf * STAGE, sw);
   };
   auto stage_b = [&](int buf, int kt) {
-    char* base = smem + buf * STAGE + A_BYTES;
-#pragma unroll
-    for (int j = 0; j < B_INSTR; ++j) {
-      const char* src = b_wave + ((size_t)j * 8 * K + (size_t)CEK_KTILE(ks, kt) * BK) * 2;
-      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                       (lds_void*)(base + (sw * B_INSTR + j) * 1024), 16, 0, 0);
-    }
+    cek_stage_rows<B_INSTR, 2>(b_wave, lane_off, K, ks, kt, smem + buf * STAGE + A_BYTES, sw);
   };
   auto stage = [&](int buf, int kt) {
     stage_a(buf, kt);
     stage_b(buf, kt);
   };
+  // MODE 4: two A buffers followed by three Bt buffers.  These two keep the
+  // issue loop written out: through cek_stage_rows the CEK_KTILE probe build
+  // of the MODE 4 kernels comes out different.
+  char* const a_base = smem;
+  char* const b_base = smem + 2 * A_BYTES;
+  auto stage_a4 = [&](int kt) {
+    char* base = a_base + (kt & 1) * A_BYTES;
+#pragma unroll
+    for (int j = 0; j < A_INSTR; ++j) {
+      const char* src = a_wave + ((size_t)j * 8 * K + (size_t)CEK_KTILE(ks, kt) * BK) * 2;
+      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off), (lds_void*)(base + (sw * A_INSTR + j) * 1024),
+                                       16, 0, 0);
+    }
+  };
+  auto stage_b4 = [&](int kt) {
+    char* base = b_base + (kt % 3) * B_BYTES;
+#pragma unroll
+    for (int j = 0; j < B_INSTR; ++j) {
+      const char* src = b_wave + ((size_t)j * 8 * K + (size_t)CEK_KTILE(ks, kt) * BK) * 2;
+      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off), (lds_void*)(base + (sw * B_INSTR + j) * 1024),
+                                       16, 0, 0);
+    }
+  };
 
+  // ---- fragments, MFMA section, barrier ----
   // Fragment read offsets (bytes) inside a stage: row (wr·128 + i·16 + l%16),
   // logical chunk s·4 + l/16, physical = logical ^ (l & 7).
   const int fr = lane & 15, fq = lane >> 4;
@@ -166,7 +177,50 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
       __syncthreads();
     }
   }
-  if constexpr (MODE == 0) {
+  // ---- main loops ----
+  const bool g1 = wave >= NWAVES / 2;  // ping-pong group G1 (MODE >= 2)
+  bf16x8 fa[2][FM], fb[2][FN];
+  // k block s of a K-tile: A rows from ab, Bt rows from bb (b_off includes A_BYTES)
+  auto ld = [&](int s, const char* ab, const char* bb) {
+#pragma unroll
+    for (int j = 0; j < FN; ++j) fb[s][j] = *(const bf16x8*)(bb + b_off[s] + j * 2048);
+#pragma unroll
+    for (int i = 0; i < FM; ++i) fa[s][i] = *(const bf16x8*)(ab + a_off[s] + i * 2048);
+  };
+  auto mma = [&](int s) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s][i], fb[s][j], acc[i][j], 0, 0, 0);
+  };
+  auto bar = [] {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  // MODE 6: the A and Bt rows of a K-tile are NCH chunks of 1 KiB (A first,
+  // then Bt, contiguous in a stage); G0's waves take the first half, G1's
+  // the second.  The probe hook CEK_KTILE does not reach this path.
+  constexpr int NCH = (A_BYTES + B_BYTES) / 1024, HALF = NCH / 2, PER_WAVE = HALF / (NWAVES / 2);
+  constexpr int A_CH = A_BYTES / 1024;
+  static_assert(MODE != 6 || PER_WAVE * (NWAVES / 2) * 2 == NCH, "even chunk split");
+  const int first_chunk = (g1 ? HALF : 0) + sw * PER_WAVE;
+  auto stage6 = [&](int kt) {
+    char* base = smem + (kt % 3) * STAGE;
+#pragma unroll
+    for (int j = 0; j < PER_WAVE; ++j) {
+      const int c = first_chunk + j;  // wave-uniform
+      const char* src = c < A_CH ? (const char*)(A + (size_t)(m0 + c * 8) * K)
+                                 : (const char*)(Bt + (size_t)(n0 + (c - A_CH) * 8) * K);
+      src += (size_t)(ks + kt) * BK * 2;
+      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off), (lds_void*)(base + c * 1024), 16, 0, 0);
+    }
+  };
+  // MODE 0: one LDS stage in flight, every wave stages, one barrier per
+  // K-tile.  (A lambda, not a branch of the dispatch below: identical code.)
+  auto single_stage_loop = [&] {
     stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -176,248 +230,92 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
       const char* base = smem + cur * STAGE;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        bf16x8 a[FM], b[FN];
-#pragma unroll
-        for (int j = 0; j < FN; ++j) b[j] = *(const bf16x8*)(base + b_off[s] + j * 2048);
-#pragma unroll
-        for (int i = 0; i < FM; ++i) a[i] = *(const bf16x8*)(base + a_off[s] + i * 2048);
+        ld(s, base, base);
         __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+        mma(s);
         __builtin_amdgcn_s_setprio(0);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
-  } else if constexpr (MODE == 2) {
-    // Ping-pong.  Interval n (between two block barriers): one group runs its
-    // 4·FM·FN MFMAs of K-tile k while the other reads K-tile k(+1)'s
-    // fragments.  G0 stages K-tile k+1 into the free LDS buffer during its
-    // read section of K-tile k and retires it (vmcnt(0)) at the end of its
-    // MFMA section, one barrier before anyone reads it; every read section
-    // ends with lgkmcnt(0) before its barrier, so a buffer is never
-    // restaged while still being read.
-    const bool g1 = wave >= NWAVES / 2;
-    bf16x8 fa[2][FM], fb[2][FN];
-    auto ldall = [&](const char* base) {
+  };
+  // Ping-pong.  Interval n (between two block barriers): one group runs its
+  // 4·FM·FN MFMAs of K-tile k while the other reads K-tile k(+1)'s
+  // fragments.  G0 stages its share of K-tile k+1 during its read section of
+  // K-tile k and retires it (vmcnt(0)) at the end of its MFMA section, one
+  // barrier before anyone reads it; every read section ends with lgkmcnt(0)
+  // before its barrier, so a buffer is never restaged while still being read.
+  // What each group stages, and where a K-tile's fragments lie:
+  //   MODE 2: G0 the whole stage k+1 into the free one of two; G1 nothing.
+  //   MODE 4: balanced DMA: G0 the A tile of k+1, G1 the Bt tile of k+2, each
+  //     during its own read section, so both groups' read sections carry the
+  //     same DMA issue cost (~60-100 cycles per 1 KiB glds) and stay shorter
+  //     than the partner's MFMA section.  Bt gets three LDS buffers
+  //     (A 2 × BM·64·2 B, Bt 3 × BN·64·2 B = 160 KiB at 256²).
+  //       WAR: both targets were last read in the previous read sections.
+  //       RAW: G0's vmcnt(0) closes its MFMA section (A k+1 before G0 reads
+  //            it); G1 ends its read section k with B k+1 retired (only k+2
+  //            in flight).
+  //   MODE 6: G0 the first half of the chunks of k+1, G1 the second half of
+  //     k+2.  Three whole stages.
+  //       WAR: a stage is refilled ≥ 2 read sections after its last read.
+  //       RAW: G0 retires its half of k+1 (vmcnt(0)) before the barrier
+  //            ending its MFMA section; G1 ends its read section k with only
+  //            its half of k+2 in flight, so k+1 is complete before G0 reads.
+  auto stage_g0 = [&](int kt) {
+    if constexpr (MODE == 2) stage(kt & 1, kt);
+    if constexpr (MODE == 4) stage_a4(kt);
+    if constexpr (MODE == 6) stage6(kt);
+  };
+  auto stage_g1 = [&](int kt) {
+    if constexpr (MODE == 4) stage_b4(kt);
+    if constexpr (MODE == 6) stage6(kt);
+  };
+  // loads G1 may leave in flight at the end of a read section: its K-tile k+2
+  constexpr int G1_AHEAD = MODE == 4 ? B_INSTR : MODE == 6 ? PER_WAVE : 0;
+  auto ldall = [&](const char* ab, const char* bb) {
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < 2; ++s) ld(s, ab, bb);
+  };
+  auto mmaall = [&]() {
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int j = 0; j < FN; ++j) fb[s][j] = *(const bf16x8*)(base + b_off[s] + j * 2048);
-#pragma unroll
-        for (int i = 0; i < FM; ++i) fa[s][i] = *(const bf16x8*)(base + a_off[s] + i * 2048);
-      }
-    };
-    auto mmaall = [&]() {
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s][i], fb[s][j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    };
-    auto bar = [] {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    if (!g1) stage(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    bar();
-    if (g1) bar();  // stagger G1 by one section
-    for (int kt = 0; kt < nk; ++kt) {
-      const char* base = smem + (kt & 1) * STAGE;
-      if (!g1 && kt + 1 < nk) stage((kt + 1) & 1, kt + 1);
-      ldall(base);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      bar();
-      mmaall();
-      if (!g1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      bar();
-    }
-    if (!g1) bar();  // equal barrier counts for both groups
-  } else if constexpr (MODE == 6) {
-    // Ping-pong with the K-tile's DMA split evenly by 1 KiB chunk: the A and
-    // Bt rows of a K-tile are NCH chunks (A first, then Bt, contiguous in a
-    // stage); G0 issues the first half for K-tile k+1 in its read section of
-    // k, G1 the second half for K-tile k+2 in its own.  Three whole stages.
-    //   WAR: a stage is refilled ≥ 2 read sections after its last read.
-    //   RAW: G0 retires its half of k+1 (vmcnt(0)) before the barrier ending
-    //        its MFMA section; G1 ends its read section k with only its half
-    //        of k+2 in flight, so k+1 is complete before G0 reads it.
-    constexpr int NCH = (A_BYTES + B_BYTES) / 1024, HALF = NCH / 2, PER_WAVE = HALF / (NWAVES / 2);
-    constexpr int A_CH = A_BYTES / 1024;
-    static_assert(PER_WAVE * (NWAVES / 2) * 2 == NCH, "even chunk split");
-    const bool g1 = wave >= NWAVES / 2;
-    const int first_chunk = (g1 ? HALF : 0) + sw * PER_WAVE;
-    auto stage6 = [&](int kt) {
-      char* base = smem + (kt % 3) * STAGE;
-#pragma unroll
-      for (int j = 0; j < PER_WAVE; ++j) {
-        const int c = first_chunk + j;  // wave-uniform
-        const char* src = c < A_CH ? (const char*)(A + (size_t)(m0 + c * 8) * K)
-                                   : (const char*)(Bt + (size_t)(n0 + (c - A_CH) * 8) * K);
-        src += (size_t)(ks + kt) * BK * 2;
-        __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off), (lds_void*)(base + c * 1024), 16, 0, 0);
-      }
-    };
-    bf16x8 fa[2][FM], fb[2][FN];
-    auto ldall = [&](int kt) {
-      const char* base = smem + (kt % 3) * STAGE;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int j = 0; j < FN; ++j) fb[s][j] = *(const bf16x8*)(base + b_off[s] + j * 2048);
-#pragma unroll
-        for (int i = 0; i < FM; ++i) fa[s][i] = *(const bf16x8*)(base + a_off[s] + i * 2048);
-      }
-    };
-    auto mmaall = [&]() {
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s][i], fb[s][j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    };
-    auto bar = [] {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    if (!g1) {
-      stage6(0);
-    } else {
-      stage6(0);
-      if (nk > 1) stage6(1);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    bar();
-    if (g1) bar();  // G1 runs one section behind
-    for (int kt = 0; kt < nk; ++kt) {
-      const bool g1_issued = g1 && kt + 2 < nk;
-      if (!g1) {
-        if (kt + 1 < nk) stage6(kt + 1);
-      } else if (g1_issued) {
-        stage6(kt + 2);
-      }
-      ldall(kt);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (g1) {
-        if (g1_issued) {
-          if constexpr (PER_WAVE == 6)
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-          else if constexpr (PER_WAVE == 8)
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-          else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-      }
-      bar();
-      mmaall();
-      if (!g1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      bar();
-    }
-    if (!g1) bar();  // equal barrier counts for both groups
+    for (int s = 0; s < 2; ++s) mma(s);
+    __builtin_amdgcn_s_setprio(0);
+  };
+  if constexpr (MODE == 0) {
+    single_stage_loop();
   } else {
-    static_assert(MODE == 4, "MODE is 0, 2, 4 or 6");
-    // Ping-pong with balanced DMA: G0 stages the A tile of K-tile k+1 and G1
-    // the Bt tile of K-tile k+2, each during its own LDS-read section, so both
-    // groups' read sections carry the same DMA issue cost (~60-100 cycles per
-    // 1 KiB glds) and stay shorter than the partner's MFMA section.  Bt gets
-    // three LDS buffers (A 2 × BM·64·2 B, Bt 3 × BN·64·2 B = 160 KiB at 256²).
-    //   WAR: both targets were last read in the previous read sections.
-    //   RAW: G0's vmcnt(0) closes its MFMA section (A k+1 before G0 reads it);
-    //        G1 ends its read section k with B k+1 retired (only k+2 in flight).
-    const bool g1 = wave >= NWAVES / 2;
-    char* const a_base = smem;
-    char* const b_base = smem + 2 * A_BYTES;
-    auto stage_a4 = [&](int kt) {
-      char* base = a_base + (kt & 1) * A_BYTES;
-#pragma unroll
-      for (int j = 0; j < A_INSTR; ++j) {
-        const char* src = a_wave + ((size_t)j * 8 * K + (size_t)CEK_KTILE(ks, kt) * BK) * 2;
-        __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off), (lds_void*)(base + (sw * A_INSTR + j) * 1024),
-                                         16, 0, 0);
-      }
-    };
-    auto stage_b4 = [&](int kt) {
-      char* base = b_base + (kt % 3) * B_BYTES;
-#pragma unroll
-      for (int j = 0; j < B_INSTR; ++j) {
-        const char* src = b_wave + ((size_t)j * 8 * K + (size_t)CEK_KTILE(ks, kt) * BK) * 2;
-        __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off), (lds_void*)(base + (sw * B_INSTR + j) * 1024),
-                                         16, 0, 0);
-      }
-    };
-    bf16x8 fa[2][FM], fb[2][FN];
-    auto ldall = [&](int kt) {
-      const char* ab = a_base + (kt & 1) * A_BYTES;
-      const char* bb = b_base + (kt % 3) * B_BYTES - A_BYTES;  // b_off includes A_BYTES
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int j = 0; j < FN; ++j) fb[s][j] = *(const bf16x8*)(bb + b_off[s] + j * 2048);
-#pragma unroll
-        for (int i = 0; i < FM; ++i) fa[s][i] = *(const bf16x8*)(ab + a_off[s] + i * 2048);
-      }
-    };
-    auto mmaall = [&]() {
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s][i], fb[s][j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    };
-    auto bar = [] {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    };
     if (!g1) {
-      stage_a4(0);
-    } else {
-      stage_b4(0);
-      if (nk > 1) stage_b4(1);
+      stage_g0(0);
+    } else if constexpr (G1_AHEAD > 0) {
+      stage_g1(0);
+      if (nk > 1) stage_g1(1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bar();
-    CEK_TS(1);
+    if constexpr (MODE == 4) CEK_TS(1);  // the timeline build stamps the production loop only
     if (g1) bar();  // G1 runs one section behind
     for (int kt = 0; kt < nk; ++kt) {
-      const bool b_issued = g1 && kt + 2 < nk;
+      // MODE 2 takes its stage's address ahead of the staging, MODE 4 and 6
+      // after it: the order the variants always had, kept for identical code
+      const char* pp_base = smem + (kt & 1) * STAGE;
+      const bool g1_issued = G1_AHEAD > 0 && g1 && kt + 2 < nk;
       if (!g1) {
-        if (kt + 1 < nk) stage_a4(kt + 1);
-      } else if (b_issued) {
-        stage_b4(kt + 2);
+        if (kt + 1 < nk) stage_g0(kt + 1);
+      } else if (g1_issued) {
+        stage_g1(kt + 2);
       }
-      ldall(kt);
+      if constexpr (MODE == 2) ldall(pp_base, pp_base);
+      if constexpr (MODE == 4) ldall(a_base + (kt & 1) * A_BYTES, b_base + (kt % 3) * B_BYTES - A_BYTES);
+      if constexpr (MODE == 6) ldall(smem + (kt % 3) * STAGE, smem + (kt % 3) * STAGE);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (g1) {
-        if (b_issued) {
-          if constexpr (B_INSTR == 8)
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-          else if constexpr (B_INSTR == 4)
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      if constexpr (G1_AHEAD > 0) {
+        if (g1) {
+          if (g1_issued)
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G1_AHEAD) : "memory");
           else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
       }
       bar();
@@ -426,7 +324,7 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
       bar();
     }
     if (!g1) bar();  // equal barrier counts for both groups
-    CEK_TS(2);
+    if constexpr (MODE == 4) CEK_TS(2);
   }
   // Epilogue: acc[i][j][r] is C(row = wr·16FM + i·16 + fq·4 + r, col = wc·16FN + j·16 + fr)
   bool store_c = true;
@@ -629,16 +527,8 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
         const char* base = smem + cur * STAGE;
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-          bf16x8 a[FM], b[FN];
-#pragma unroll
-          for (int j = 0; j < FN; ++j) b[j] = *(const bf16x8*)(base + b_off[s2] + j * 2048);
-#pragma unroll
-          for (int i = 0; i < FM; ++i) a[i] = *(const bf16x8*)(base + a_off[s2] + i * 2048);
-#pragma unroll
-          for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+          ld(s2, base, base);
+          mma(s2);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -744,84 +634,48 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
 
 }  // namespace
 
-#define CEK_GEMM_KERNEL(NAME, WM, WN, FM, FN, MODE)                                              \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                \
-      const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, CEK_HIDDEN) {              \
-    __shared__ __attribute__((aligned(16))) char smem[2 * (WM * 16 * FM + WN * 16 * FN) * 64 * 2]; \
-    gemm_tile<WM, WN, FM, FN, MODE>(dims, A, Bt, C, smem, __cek_off);                              \
-  }
-
-#define CEK_GEMM_SK_KERNEL(NAME, WM, WN, FM, FN, MODE)                                           \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                \
-      const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, float* W, int* tile_cnt,    \
-      CEK_HIDDEN) {                                                                                \
-    __shared__ __attribute__((aligned(16))) char smem[2 * (WM * 16 * FM + WN * 16 * FN) * 64 * 2]; \
-    gemm_tile<WM, WN, FM, FN, MODE, true>(dims, A, Bt, C, smem, __cek_off, W, tile_cnt);           \
+// One kernel per variant.  SK = 1 kernels take the split-K workspace W and the
+// per-tile flag words tile_cnt after C.
+#define CEK_WS_PARAMS_0
+#define CEK_WS_PARAMS_1 float *W, int *tile_cnt,
+#define CEK_WS_ARGS_0
+#define CEK_WS_ARGS_1 , W, tile_cnt
+#define CEK_GEMM_KERNEL(NAME, WM, WN, FM, FN, MODE, SK, XCH, ROWC)                                          \
+  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                           \
+      const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, CEK_WS_PARAMS_##SK CEK_HIDDEN) {      \
+    __shared__ __attribute__((aligned(16))) char smem[gemm_lds_bytes(WM, WN, FM, FN, MODE)];                  \
+    gemm_tile<WM, WN, FM, FN, MODE, SK, XCH, ROWC>(dims, A, Bt, C, smem, __cek_off CEK_WS_ARGS_##SK);         \
   }
 
 // Split-K ping-pong variants (dims[4] = S splits; K/64 divisible by S):
 // strongly scaled slices keep one 256-row tile per CU busy instead of
 // leaving CUs idle (8 GPUs × 1024 rows of an 8192² problem = 128 tiles).
-CEK_GEMM_SK_KERNEL(cek_sgemm_bf16_256x256pp_sk, 2, 4, 8, 4, 2)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pp_sk, 2, 4, 8, 4, 2, 1, 0, 0)
 // balanced-DMA split-K (three Bt buffers: 160 KiB LDS)
-extern "C" __global__ __launch_bounds__(512) void cek_sgemm_bf16_256x256pb_sk(
-    const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, float* W, int* tile_cnt, CEK_HIDDEN) {
-  __shared__ __attribute__((aligned(16))) char smem[(2 * 256 + 3 * 256) * 64 * 2];
-  gemm_tile<2, 4, 8, 4, 4, true>(dims, A, Bt, C, smem, __cek_off, W, tile_cnt);
-}
-
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sk, 2, 4, 8, 4, 4, 1, 0, 0)
 // uneven split-K = 2 with a one-way hand-over (dims[5] = the helper's
 // K-tile deficit): the helper's partial stores overlap the owner's last
 // K-tiles instead of both sides' exchange landing at the end of the launch
-extern "C" __global__ __launch_bounds__(512) void cek_sgemm_bf16_256x256pb_sw(
-    const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, float* W, int* tile_cnt, CEK_HIDDEN) {
-  __shared__ __attribute__((aligned(16))) char smem[(2 * 256 + 3 * 256) * 64 * 2];
-  gemm_tile<2, 4, 8, 4, 4, true, 3>(dims, A, Bt, C, smem, __cek_off, W, tile_cnt);
-}
-
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sw, 2, 4, 8, 4, 4, 1, 3, 0)
 // the same with the row halves exchanged at the end (XCH 4): the owner's
 // tail carries 384 KiB instead of 512, the helper stores half of C
-extern "C" __global__ __launch_bounds__(512) void cek_sgemm_bf16_256x256pb_sh(
-    const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, float* W, int* tile_cnt, CEK_HIDDEN) {
-  __shared__ __attribute__((aligned(16))) char smem[(2 * 256 + 3 * 256) * 64 * 2];
-  gemm_tile<2, 4, 8, 4, 4, true, 4>(dims, A, Bt, C, smem, __cek_off, W, tile_cnt);
-}
-
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sh, 2, 4, 8, 4, 4, 1, 4, 0)
 // halves exchanged with both partial stores in flight at once (XCH 5):
 // meant for an even split (dims[5] = 0), both sides ending together
-extern "C" __global__ __launch_bounds__(512) void cek_sgemm_bf16_256x256pb_ss(
-    const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, float* W, int* tile_cnt, CEK_HIDDEN) {
-  __shared__ __attribute__((aligned(16))) char smem[(2 * 256 + 3 * 256) * 64 * 2];
-  gemm_tile<2, 4, 8, 4, 4, true, 5>(dims, A, Bt, C, smem, __cek_off, W, tile_cnt);
-}
-
-#define CEK_GEMM_B3_KERNEL(NAME, WM, WN, FM, FN, MODE)                                              \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                    \
-      const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, CEK_HIDDEN) {                  \
-    __shared__ __attribute__((aligned(16))) char smem[(2 * WM * 16 * FM + 3 * WN * 16 * FN) * 64 * 2]; \
-    gemm_tile<WM, WN, FM, FN, MODE>(dims, A, Bt, C, smem, __cek_off);                                  \
-  }
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_ss, 2, 4, 8, 4, 4, 1, 5, 0)
 
 // Balanced-DMA ping-pong (MODE 4):
 // 160 KiB LDS at 256², 128 KiB at 256×128.
-CEK_GEMM_B3_KERNEL(cek_sgemm_bf16_256x256pb, 2, 4, 8, 4, 4)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb, 2, 4, 8, 4, 4, 0, 0, 0)
 // the same with C row-major ([M][N]) through an LDS turn-around per wave
-extern "C" __global__ __launch_bounds__(512) void cek_sgemm_bf16_256x256pbr(
-    const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, CEK_HIDDEN) {
-  __shared__ __attribute__((aligned(16))) char smem[(2 * 256 + 3 * 256) * 64 * 2];
-  gemm_tile<2, 4, 8, 4, 4, false, 0, true>(dims, A, Bt, C, smem, __cek_off);
-}
-CEK_GEMM_B3_KERNEL(cek_sgemm_bf16_256x128pb, 4, 2, 4, 4, 4)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pbr, 2, 4, 8, 4, 4, 0, 0, 1)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x128pb, 4, 2, 4, 4, 4, 0, 0, 0)
 
 // Even chunk-split DMA with three whole stages (MODE 6): 144 KiB at 256×128.
-extern "C" __global__ __launch_bounds__(512) void cek_sgemm_bf16_256x128pe(
-    const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, CEK_HIDDEN) {
-  __shared__ __attribute__((aligned(16))) char smem[3 * (256 + 128) * 64 * 2];
-  gemm_tile<4, 2, 4, 4, 6>(dims, A, Bt, C, smem, __cek_off);
-}
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x128pe, 4, 2, 4, 4, 6, 0, 0, 0)
 
 // 256×256 tiles, 8 waves (2×4, 128×64 each), 128 KiB LDS, 1 block/CU.
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256, 2, 4, 8, 4, 0)
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pp, 2, 4, 8, 4, 2)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256, 2, 4, 8, 4, 0, 0, 0, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pp, 2, 4, 8, 4, 2, 0, 0, 0)
 // 128×128 tiles, 4 waves (2×2, 64×64 each), 64 KiB LDS, 2 blocks/CU.
-CEK_GEMM_KERNEL(cek_sgemm_bf16_128x128, 2, 2, 4, 4, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_128x128, 2, 2, 4, 4, 0, 0, 0, 0)

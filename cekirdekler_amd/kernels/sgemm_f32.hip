@@ -18,7 +18,7 @@
 // to the t-th of four MFMAs: MFMA t then sums over k ∈ {t, 4+t, 8+t, 12+t}
 // for A and B alike, and the four together cover the k block exactly.
 // One ds_read_b128 per operand fragment per 16 k, four MFMAs per read.
-#include "cek_kernel.h"
+#include "gemm_parts.h"
 
 namespace {
 
@@ -39,32 +39,24 @@ __device__ __forceinline__ void gemm_f32_tile(const int* __restrict__ dims, cons
   const long long t = (long long)cek_xcd_remap(blockIdx.x, gridDim.x) + off / NT;
   const int ntn = N / BN, ntm = M / BM;
   int tm, tn;
-  // a launch wider than the tile grid (a host-side range error) must not
-  // read or write past A, B or C: surplus work-groups leave at once
-  if (t >= (long long)ntm * ntn) return;
-  cek_tile_coords(t, ntm, ntn, GM, dims[6], tm, tn);
+  if (!cek_tile_lookup(dims, GM, t, ntm, ntn, tm, tn)) return;
   const int m0 = tm * BM, n0 = tn * BN;
 
-  // staging: lane l of a wave instruction lands at row ins·8 + l/8, physical
-  // 16-B chunk l%8, which holds logical chunk (l%8) ^ (row & 7)
-  const int lrow = lane >> 3, lchunk = (lane & 7) ^ (lrow & 7);
-  const unsigned lane_off = (unsigned)(lrow * K + lchunk * 4) * 4u;
+  const unsigned lane_off = cek_stage_lane_off<4>(lane, K);
   const char* a_wave = (const char*)(A + (size_t)(m0 + wave * A_INSTR * 8) * K);
   const char* b_wave = (const char*)(Bt + (size_t)(n0 + wave * B_INSTR * 8) * K);
   auto stage = [&](int buf, int kt) {
     char* base = smem + buf * STAGE;
-#pragma unroll
-    for (int j = 0; j < A_INSTR; ++j) {
-      const char* src = a_wave + ((size_t)j * 8 * K + (size_t)kt * BK) * 4;
-      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                       (lds_void*)(base + (wave * A_INSTR + j) * 1024), 16, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < B_INSTR; ++j) {
-      const char* src = b_wave + ((size_t)j * 8 * K + (size_t)kt * BK) * 4;
-      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                       (lds_void*)(base + A_BYTES + (wave * B_INSTR + j) * 1024), 16, 0, 0);
-    }
+    cek_stage_rows<A_INSTR, 4>(a_wave, lane_off, K, 0, kt, base, wave);
+    cek_stage_rows<B_INSTR, 4>(b_wave, lane_off, K, 0, kt, base + A_BYTES, wave);
+  };
+  // piece g of a K-tile's A_INSTR + B_INSTR wave instructions, on its own
+  auto stage_one = [&](int buf, int kt, int g) {
+    char* base = smem + buf * STAGE;
+    if (g < A_INSTR)
+      cek_stage_rows<1, 4, A_INSTR>(a_wave, lane_off, K, 0, kt, base, wave, g);
+    else
+      cek_stage_rows<1, 4, B_INSTR>(b_wave, lane_off, K, 0, kt, base + A_BYTES, wave, g - A_INSTR);
   };
 
   // fragment offsets: row (wr·16FM + i·16 + l%16), logical chunk s·4 + l/16
@@ -115,19 +107,6 @@ __device__ __forceinline__ void gemm_f32_tile(const int* __restrict__ dims, cons
     constexpr int NGLDS = A_INSTR + B_INSTR;
     constexpr int NGROUPS = PIPE == 4 ? 4 : 8;  // PIPE 5 spreads like PIPE 3
     constexpr int PER_GROUP = (NGLDS + NGROUPS - 1) / NGROUPS;
-    auto stage_one = [&](int buf, int kt, int g) {
-      char* base = smem + buf * STAGE;
-      if (g < A_INSTR) {
-        const char* src = a_wave + ((size_t)g * 8 * K + (size_t)kt * BK) * 4;
-        __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                         (lds_void*)(base + (wave * A_INSTR + g) * 1024), 16, 0, 0);
-      } else {
-        const int j = g - A_INSTR;
-        const char* src = b_wave + ((size_t)j * 8 * K + (size_t)kt * BK) * 4;
-        __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                         (lds_void*)(base + A_BYTES + (wave * B_INSTR + j) * 1024), 16, 0, 0);
-      }
-    };
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = kt & 1;
       const char* base = smem + cur * STAGE;
@@ -180,19 +159,6 @@ __device__ __forceinline__ void gemm_f32_tile(const int* __restrict__ dims, cons
     constexpr int BARG = PIPE == 7 ? 6 : 7;
     constexpr int DMAG = PIPE == 8 ? 7 : 4;
     constexpr int NRD = FM + FN, PER_RD = (NRD + 3) / 4;
-    auto stage_one = [&](int buf, int kt, int g) {
-      char* base = smem + buf * STAGE;
-      if (g < A_INSTR) {
-        const char* src = a_wave + ((size_t)g * 8 * K + (size_t)kt * BK) * 4;
-        __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                         (lds_void*)(base + (wave * A_INSTR + g) * 1024), 16, 0, 0);
-      } else {
-        const int j = g - A_INSTR;
-        const char* src = b_wave + ((size_t)j * 8 * K + (size_t)kt * BK) * 4;
-        __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                         (lds_void*)(base + A_BYTES + (wave * B_INSTR + j) * 1024), 16, 0, 0);
-      }
-    };
     f32x4 fa[2][FM], fb[2][FN];
     ld(fa[0], fb[0], smem, 0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -295,30 +261,16 @@ __device__ __forceinline__ void gemm_f32w_tile(const int* __restrict__ dims, con
   const long long t = (long long)cek_xcd_remap(blockIdx.x, gridDim.x) + off / NT;
   const int ntn = N / BN, ntm = M / BM;
   int tm, tn;
-  // a launch wider than the tile grid (a host-side range error) must not
-  // read or write past A, B or C: surplus work-groups leave at once
-  if (t >= (long long)ntm * ntn) return;
-  cek_tile_coords(t, ntm, ntn, GM, dims[6], tm, tn);
+  if (!cek_tile_lookup(dims, GM, t, ntm, ntn, tm, tn)) return;
   const int m0 = tm * BM, n0 = tn * BN;
 
-  const int lrow = lane >> 3, lchunk = (lane & 7) ^ (lrow & 7);
-  const unsigned lane_off = (unsigned)(lrow * K + lchunk * 4) * 4u;
+  const unsigned lane_off = cek_stage_lane_off<4>(lane, K);
   const char* a_wave = (const char*)(A + (size_t)(m0 + wave * A_INSTR * 8) * K);
   const char* b_wave = (const char*)(Bt + (size_t)(n0 + wave * B_INSTR * 8) * K);
   auto stage = [&](int buf, int kt) {
     char* base = smem + buf * STAGE;
-#pragma unroll
-    for (int j = 0; j < A_INSTR; ++j) {
-      const char* src = a_wave + ((size_t)j * 8 * K + (size_t)kt * BK) * 4;
-      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                       (lds_void*)(base + (wave * A_INSTR + j) * 1024), 16, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < B_INSTR; ++j) {
-      const char* src = b_wave + ((size_t)j * 8 * K + (size_t)kt * BK) * 4;
-      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off),
-                                       (lds_void*)(base + A_BYTES + (wave * B_INSTR + j) * 1024), 16, 0, 0);
-    }
+    cek_stage_rows<A_INSTR, 4>(a_wave, lane_off, K, 0, kt, base, wave);
+    cek_stage_rows<B_INSTR, 4>(b_wave, lane_off, K, 0, kt, base + A_BYTES, wave);
   };
 
   // fragment offsets for 8-deep block kb: row (wr·32FM + i·32 + l%32),
@@ -433,10 +385,7 @@ __device__ __forceinline__ void gemm_f32_direct(const int* __restrict__ dims, co
   const long long t = (long long)cek_xcd_remap(blockIdx.x, gridDim.x) + off / NT;
   const int ntn = N / BN, ntm = M / BM;
   int tm, tn;
-  // a launch wider than the tile grid (a host-side range error) must not
-  // read or write past A, B or C: surplus work-groups leave at once
-  if (t >= (long long)ntm * ntn) return;
-  cek_tile_coords(t, ntm, ntn, GM, dims[6], tm, tn);
+  if (!cek_tile_lookup(dims, GM, t, ntm, ntn, tm, tn)) return;
   const int fr = lane & 15, fq = lane >> 4;
   const float* a_base = A + (size_t)tm * BM * K;
   const float* b_base = Bt + (size_t)tn * BN * K;
@@ -561,32 +510,31 @@ CEK_GEMM_F32G_KERNEL(cek_sgemm_f32_256x256g8i, 2, 4, 8, 4, 2)  // loads spread b
 CEK_GEMM_F32G_KERNEL(cek_sgemm_f32_256x256g8h, 2, 4, 8, 4, 3)  // spread over the first half
 CEK_GEMM_F32G_KERNEL(cek_sgemm_f32_256x256g8q, 2, 4, 8, 4, 4)  // spread over the first quarter
 
-#define CEK_GEMM_F32_KERNEL(NAME, WM, WN, FM, FN, PIPE)                                           \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                 \
-      const int* dims, const float* A, const float* Bt, float* C, CEK_HIDDEN) {                     \
-    __shared__ __attribute__((aligned(16))) char smem[2 * (WM * 16 * FM + WN * 16 * FN) * 32 * 4]; \
-    gemm_f32_tile<WM, WN, FM, FN, PIPE>(dims, A, Bt, C, smem, __cek_off);                           \
+// LDS-staged kernels: TILE is the tile function, R its MFMA fragment's rows
+// (16 or 32), the trailing arguments its template arguments after WM, WN, FM, FN.
+// Two stages of (BM + BN) rows of 128 B.
+constexpr int gemm_f32_lds_bytes(int R, int WM, int WN, int FM, int FN) {
+  return 2 * (WM * R * FM + WN * R * FN) * 128;
+}
+#define CEK_GEMM_F32_KERNEL(NAME, TILE, R, WM, WN, FM, FN, ...)                                    \
+  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                  \
+      const int* dims, const float* A, const float* Bt, float* C, CEK_HIDDEN) {                      \
+    __shared__ __attribute__((aligned(16))) char smem[gemm_f32_lds_bytes(R, WM, WN, FM, FN)];        \
+    TILE<WM, WN, FM, FN, ##__VA_ARGS__>(dims, A, Bt, C, smem, __cek_off);                            \
   }
 
 // 128×128 tiles, 4 waves (2×2, 64×64 each), 64 KiB LDS: two work-groups per CU.
-CEK_GEMM_F32_KERNEL(cek_sgemm_f32_128x128, 2, 2, 4, 4, 0)
+CEK_GEMM_F32_KERNEL(cek_sgemm_f32_128x128, gemm_f32_tile, 16, 2, 2, 4, 4, 0)
 // 256×128 tiles, 8 waves (4×2, 64×64 each), 96 KiB LDS.
-CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x128, 4, 2, 4, 4, 0)
+CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x128, gemm_f32_tile, 16, 4, 2, 4, 4, 0)
 // 256×256 tiles, 8 waves (2×4, 128×64 each), 128 KiB LDS.
-CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x256, 2, 4, 8, 4, 0)
+CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x256, gemm_f32_tile, 16, 2, 4, 8, 4, 0)
 // fragment reads of k block 1 between block 0's MFMA groups (production:
 // profiles/gemm_f32_findings.md); ib7: barrier ahead of the last MFMA groups;
 // 256x128ie: every LDS-DMA piece within the first k block's MFMAs
-CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x256ir, 2, 4, 8, 4, 5)
-CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x256ib7, 2, 4, 8, 4, 8)
-CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x128ie, 4, 2, 4, 4, 4)
+CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x256ir, gemm_f32_tile, 16, 2, 4, 8, 4, 5)
+CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x256ib7, gemm_f32_tile, 16, 2, 4, 8, 4, 8)
+CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x128ie, gemm_f32_tile, 16, 4, 2, 4, 4, 4)
 
 // 32×32×2 form with register double-buffered fragments (gemm_f32w_tile).
-#define CEK_GEMM_F32W_KERNEL(NAME, WM, WN, FM, FN)                                                 \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                  \
-      const int* dims, const float* A, const float* Bt, float* C, CEK_HIDDEN) {                      \
-    __shared__ __attribute__((aligned(16))) char smem[2 * (WM * 32 * FM + WN * 32 * FN) * 32 * 4];  \
-    gemm_f32w_tile<WM, WN, FM, FN>(dims, A, Bt, C, smem, __cek_off);                                 \
-  }
-
-CEK_GEMM_F32W_KERNEL(cek_sgemm_f32_256x256w, 2, 4, 4, 2)  // 8 waves, 128×64 each, 128 KiB LDS
+CEK_GEMM_F32_KERNEL(cek_sgemm_f32_256x256w, gemm_f32w_tile, 32, 2, 4, 4, 2)  // 8 waves, 128×64 each, 128 KiB LDS

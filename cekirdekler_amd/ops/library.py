@@ -54,7 +54,10 @@ ARITY = {
 def code_object(name: str) -> str:
     path = os.path.join(kernel_dir(), name + ".hsaco")
     src = os.path.join(kernel_dir(), name + ".hip")
-    stale = os.path.exists(src) and (not os.path.exists(path) or os.path.getmtime(src) > os.path.getmtime(path))
+    # the rule of build_native.build_kernels: the source and every header beside it
+    deps = [src] + [os.path.join(kernel_dir(), f) for f in os.listdir(kernel_dir()) if f.endswith(".h")]
+    stale = os.path.exists(src) and (not os.path.exists(path)
+                                     or any(os.path.getmtime(d) > os.path.getmtime(path) for d in deps))
     if stale:
         from .. import build_native
 
