@@ -33,6 +33,10 @@ from ._native import cek
 # --------------------------------------------------------------------------- dtypes
 
 BFLOAT16 = "bfloat16"
+# OCP e4m3fn (gfx950's fp8; not the MI300 fnuz encoding): uint8 storage plus
+# the ``is_fp8`` flag, as bf16 is uint16 storage plus ``is_bf16``
+FLOAT8_E4M3FN = "float8_e4m3fn"
+_FP8_NAMES = ("float8_e4m3fn", "fp8", "e4m3")
 
 _DTYPES = {
     "float32": np.float32, "float": np.float32, "f32": np.float32,
@@ -53,6 +57,8 @@ def _resolve_dtype(dtype) -> tuple[np.dtype, bool]:
         key = dtype.lower()
         if key in ("bfloat16", "bf16"):
             return np.dtype(np.uint16), True
+        if key in _FP8_NAMES:
+            return np.dtype(np.uint8), False
         if key in _DTYPES:
             return np.dtype(_DTYPES[key]), False
     try:
@@ -61,10 +67,24 @@ def _resolve_dtype(dtype) -> tuple[np.dtype, bool]:
         if isinstance(dtype, torch.dtype):
             if dtype == torch.bfloat16:
                 return np.dtype(np.uint16), True
+            if dtype == torch.float8_e4m3fn:
+                return np.dtype(np.uint8), False
             return np.dtype(torch.empty(0, dtype=dtype).numpy().dtype), False
     except Exception:  # pragma: no cover
         pass
     return np.dtype(dtype), False
+
+
+def _is_fp8(dtype) -> bool:
+    """``dtype`` names fp8 e4m3fn (storage: :func:`_resolve_dtype` gives uint8)."""
+    if isinstance(dtype, str):
+        return dtype.lower() in _FP8_NAMES
+    try:
+        import torch
+
+        return isinstance(dtype, torch.dtype) and dtype == torch.float8_e4m3fn
+    except ImportError:  # pragma: no cover
+        return False
 
 
 _uid_counter = itertools.count(1)
@@ -103,6 +123,7 @@ class FastArr:
 
     def __init__(self, n: int, dtype=np.float32, alignment: int = 4096):
         np_dtype, self.is_bf16 = _resolve_dtype(dtype)
+        self.is_fp8 = _is_fp8(dtype)
         if n <= 0:
             raise ValueError("FastArr length must be positive")
         self._n = int(n)
@@ -204,6 +225,7 @@ ClLongArray = _typed_fastarr("ClLongArray", np.int64)
 ClByteArray = _typed_fastarr("ClByteArray", np.uint8)
 ClCharArray = _typed_fastarr("ClCharArray", np.uint16)
 ClBf16Array = _typed_fastarr("ClBf16Array", BFLOAT16)
+ClFp8Array = _typed_fastarr("ClFp8Array", FLOAT8_E4M3FN)
 
 
 # --------------------------------------------------------------------------- ClArray
@@ -234,21 +256,23 @@ class ClArray:
         self._np: Optional[np.ndarray] = None
         self._torch_ref = None
         self.is_bf16 = False
+        self.is_fp8 = False
         if data is None:
             self._np = None
         elif isinstance(data, (int, np.integer)):
             n = int(data)
             if fast is False:
                 np_dtype, self.is_bf16 = _resolve_dtype(dtype)
+                self.is_fp8 = _is_fp8(dtype)
                 self._np = np.zeros(n, np_dtype)
             else:
                 self._fast = FastArr(n, dtype or np.float32, alignment)
-                self.is_bf16 = self._fast.is_bf16
+                self.is_bf16, self.is_fp8 = self._fast.is_bf16, self._fast.is_fp8
         elif isinstance(data, FastArr):
             self._fast = data
-            self.is_bf16 = data.is_bf16
+            self.is_bf16, self.is_fp8 = data.is_bf16, data.is_fp8
         elif isinstance(data, ClArray):
-            self._fast, self._np, self.is_bf16 = data._fast, data._np, data.is_bf16
+            self._fast, self._np, self.is_bf16, self.is_fp8 = data._fast, data._np, data.is_bf16, data.is_fp8
         else:
             self._wrap_host(data, dtype)
         # reference defaults (ClArray.cs:838-845)
@@ -293,6 +317,9 @@ class ClArray:
                 if t.dtype == torch.bfloat16:
                     self.is_bf16 = True
                     self._np = t.view(torch.int16).numpy().view(np.uint16)
+                elif t.dtype == torch.float8_e4m3fn:
+                    self.is_fp8 = True
+                    self._np = t.view(torch.uint8).numpy()
                 else:
                     self._np = t.numpy()
                 return
@@ -301,6 +328,7 @@ class ClArray:
         arr = np.asarray(data)
         if dtype is not None:
             np_dtype, self.is_bf16 = _resolve_dtype(dtype)
+            self.is_fp8 = _is_fp8(dtype)
             if arr.dtype != np_dtype:
                 arr = arr.astype(np_dtype)
         if not arr.flags.c_contiguous:
@@ -327,7 +355,7 @@ class ClArray:
         keeping the contents (reference ``fastArr`` setter, ClArray.cs:889)."""
         if on and self._fast is None:
             old = self.array
-            f = FastArr(len(old), BFLOAT16 if self.is_bf16 else old.dtype, self.alignment_bytes)
+            f = FastArr(len(old), self._storage_dtype(old.dtype), self.alignment_bytes)
             f.array[:] = old
             self._release_device()
             self._fast, self._np, self._torch_ref = f, None, None
@@ -351,7 +379,7 @@ class ClArray:
         self._release_device()
         if self._fast is not None:
             self._fast.dispose()
-            self._fast = FastArr(n, BFLOAT16 if self.is_bf16 else np_dtype, self.alignment_bytes)
+            self._fast = FastArr(n, self._storage_dtype(np_dtype), self.alignment_bytes)
         else:
             self._np = np.zeros(n, np_dtype)
         self._uid = next(_uid_counter)
@@ -363,9 +391,19 @@ class ClArray:
     Count = Length
     arrayLength = Length
 
+    def _storage_dtype(self, np_dtype):
+        """What to allocate a FastArr of this array's element type with."""
+        return BFLOAT16 if self.is_bf16 else FLOAT8_E4M3FN if self.is_fp8 else np_dtype
+
     @property
     def dtype(self):
-        return BFLOAT16 if self.is_bf16 else self.array.dtype
+        return self._storage_dtype(self.array.dtype)
+
+    @property
+    def dtype_name(self) -> str:
+        """The element type's name: ``"bfloat16"`` / ``"float8_e4m3fn"`` for
+        the flagged bit-pattern arrays, numpy's name otherwise."""
+        return str(self.dtype)
 
     @property
     def itemsize(self) -> int:
@@ -429,13 +467,18 @@ class ClArray:
     copy_from = CopyFrom
 
     def as_torch(self):
-        """Zero-copy torch CPU tensor view (bf16 arrays come back as bfloat16)."""
+        """Zero-copy torch CPU tensor view (bf16 arrays come back as bfloat16,
+        fp8 arrays as float8_e4m3fn)."""
         import torch
 
         t = torch.from_numpy(self.array)
         if self.is_bf16:
             t = t.view(torch.bfloat16)
+        elif self.is_fp8:
+            t = t.view(torch.float8_e4m3fn)
         return t
+
+    to_torch = as_torch
 
     @staticmethod
     def wrap_array_of_structs(structs: np.ndarray) -> "ClArray":

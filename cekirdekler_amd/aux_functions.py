@@ -26,6 +26,26 @@ __device__ inline unsigned short cek_f32_to_bf16(float f) {   // round to neares
   unsigned int r = 0x7fffu + ((c.u >> 16) & 1u);
   return (unsigned short)((c.u + r) >> 16); }
 """,
+    # OCP e4m3fn (the codec of ops/gemm.py: round to nearest even, subnormals
+    # of 2^-9 kept, finite values beyond 448 saturate, NaN = 0x7f)
+    "fp8": r"""
+__device__ inline float cek_fp8_e4m3_to_f32(unsigned char h) {
+  const unsigned int s = ((unsigned int)(h & 0x80u)) << 24, e = (h >> 3) & 15u, m = h & 7u;
+  union { unsigned int u; float f; } c;
+  if (e == 0u) { c.f = (float)m * 0.001953125f; c.u |= s; return c.f; }   // subnormal: m * 2^-9
+  if (e == 15u && m == 7u) { c.u = s | 0x7fc00000u; return c.f; }
+  c.u = s | ((e + 120u) << 23) | (m << 20); return c.f; }
+__device__ inline unsigned char cek_f32_to_fp8_e4m3(float f) {
+  union { unsigned int u; float f; } c; c.f = f;
+  const unsigned int s = (c.u >> 24) & 0x80u, a = c.u & 0x7fffffffu;
+  if (a > 0x7f800000u) return (unsigned char)0x7f;                   // NaN
+  if (a >= 0x43e00000u) return (unsigned char)(s | 0x7eu);           // |f| >= 448 saturates
+  if (a < 0x3c800000u) {                                             // |f| < 2^-6: units of 2^-9
+    c.u = a; c.f = c.f * 512.0f + 8388608.0f;                        // 2^23: nearest-even integer
+    return (unsigned char)(s | (c.u & 15u)); }
+  const unsigned int r = a + 0x7ffffu + ((a >> 20) & 1u);            // nearest even at 3 mantissa bits
+  return (unsigned char)(s | ((r >> 20) - (120u << 3))); }
+""",
     # 64-wide wavefront reduction (CDNA4 wave64; DPP/swizzle via __shfl_xor)
     "wave_sum": r"""
 #ifdef CEK_GPU

@@ -38,8 +38,8 @@ void Cores::gemm_host_shells(int local_dev, const std::string& kernel, const Arr
   if (capturing_) throw Error("gemm_host_shells: not inside a graph capture");
   if (panels < 1 || M % panels || N % panels) throw Error("gemm_host_shells: M and N must split into panels");
   const int PM = M / panels, PN = N / panels;
-  const int es = A.elem_size;  // 2: bf16 operands (BK = 64), 4: fp32 operands (BK = 32)
-  if (PM % BM || PN % BN || L <= 0 || (es != 2 && es != 4) || K % (es == 2 ? 64 : 32))
+  const int es = A.elem_size;  // 1: fp8 operands (BK = 128), 2: bf16 (BK = 64), 4: fp32 (BK = 32)
+  if (PM % BM || PN % BN || L <= 0 || (es != 1 && es != 2 && es != 4) || K % (128 / es))
     throw Error("gemm_host_shells: panel sizes must be whole tiles and K whole K-tiles");
   if (B.elem_size != es || A.bytes != 1ull * es * M * K || B.bytes != 1ull * es * N * K ||
       C.bytes != 4ull * M * N || C.elem_size != 4)

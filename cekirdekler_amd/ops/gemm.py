@@ -1,5 +1,5 @@
 """Range-partitioned GEMMs: bf16 (the "SGEMM 8192² bf16" config of
-BASELINE.json) and fp32 on the fp32 matrix cores.
+BASELINE.json), fp32 on the fp32 matrix cores and fp8 (OCP e4m3fn).
 
 ``C = A · Bᵀ`` with A ``[M][K]`` and Bt ``[N][K]`` bf16 row-major, C fp32 in
 tile-major layout (see ``kernels/sgemm_bf16.hip``).  The global range is one
@@ -126,6 +126,24 @@ F32_TILES = {
     "128x128": (128, 128, 256, "cek_sgemm_f32_128x128"),
 }
 
+# fp8 e4m3fn tiles (kernels/sgemm_fp8.hip): BK = 128, C in fragment order
+# like the bf16 tiles.  No split-K or exchange variants.  Throughput at 8192³
+# beside the bf16 256x256pb of the same run (1487 TF/s): profiles/gemm_fp8.md.
+FP8_TILES = {
+    # the bf16 production structure (balanced-DMA ping-pong) with four
+    # v_mfma_f32_16x16x32_fp8_fp8 steps per K-tile, the bf16 matrix rate:
+    # 1997 TF/s (1.34× bf16: half the staging bytes and barriers per flop)
+    "256x256pb": (256, 256, 512, "cek_sgemm_fp8_256x256pb"),
+    # the same with v_mfma_scale_f32_16x16x128_f8f6f4 at unit scales, one
+    # instruction per fragment pair and K-tile, the fp8 matrix rate:
+    # 2751 TF/s (1.85× bf16), the GemmFp8 default
+    "256x256pbx": (256, 256, 512, "cek_sgemm_fp8_256x256pbx"),
+    # one LDS stage in flight, 4 waves, the simple kernel the others are
+    # judged against: 1709 TF/s (1.15× bf16)
+    "128x128": (128, 128, 256, "cek_sgemm_fp8_128x128"),
+}
+FP8_TILE_WAVES = {"256x256pb": (2, 4, 8, 4), "256x256pbx": (2, 4, 8, 4), "128x128": (2, 2, 4, 4)}
+
 # tiles whose kernel stores C row-major ([M][N]) instead of tile-major
 ROW_MAJOR_TILES = {"256x256pbr"}
 # tiles with a split-K kernel variant ("<kernel>_sk", arrays + W + counters)
@@ -146,6 +164,51 @@ def to_bf16_bits(x: np.ndarray) -> np.ndarray:
 
 def from_bf16_bits(b: np.ndarray) -> np.ndarray:
     return (b.astype(np.uint32) << 16).view(np.float32)
+
+
+def _fp8_e4m3_table() -> np.ndarray:
+    c = np.arange(256)
+    e, m = (c >> 3) & 15, (c & 7).astype(np.float64)
+    v = np.where(e == 0, m * 2.0 ** -9, (1 + m / 8) * 2.0 ** (e - 7.0))
+    v[(c & 0x7F) == 0x7F] = np.nan
+    return np.where(c & 0x80, -v, v).astype(np.float32)
+
+
+_FP8_E4M3 = _fp8_e4m3_table()
+
+
+def to_fp8_e4m3_bits(x: np.ndarray) -> np.ndarray:
+    """fp32 → OCP e4m3fn bit patterns, as uint8: round to nearest even
+    (subnormals included: the smallest is 2⁻⁹), NaN → ``0x7F``, the sign of
+    zero kept.  Finite values beyond ±448 and ±inf SATURATE to ±448
+    (``0x7E`` / ``0xFE``); torch's CPU conversion turns what rounds past 448
+    into NaN instead, and agrees bit for bit everywhere else."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    a = u & np.uint32(0x7FFFFFFF)
+    sign = ((u >> 24) & np.uint32(0x80)).astype(np.uint8)
+    # normal range: nearest even at 3 mantissa bits, exponent rebiased 127 → 7
+    norm = ((a + np.uint32(0x7FFFF) + ((a >> 20) & np.uint32(1))) >> 20).astype(np.int64) - (120 << 3)
+    # below 2⁻⁶: units of 2⁻⁹ (8 units = code 0x08 = 2⁻⁶, the first normal)
+    small = a < np.uint32(0x3C800000)
+    sub = np.rint(np.where(small, a, np.uint32(0)).view(np.float32) * np.float32(512.0)).astype(np.int64)
+    code = np.where(small, sub, norm)
+    code = np.where(a >= np.uint32(0x43E00000), 0x7E, code).astype(np.uint8) | sign  # |x| >= 448, inf
+    return np.where(a > np.uint32(0x7F800000), np.uint8(0x7F), code).astype(np.uint8)
+
+
+def from_fp8_e4m3_bits(b: np.ndarray) -> np.ndarray:
+    """OCP e4m3fn bit patterns (uint8) → fp32 (``0x7F`` / ``0xFF`` → NaN)."""
+    return _FP8_E4M3[np.asarray(b, dtype=np.uint8)]
+
+
+def decode_operand(arr: ClArray) -> np.ndarray:
+    """The host array of a GEMM operand as numbers: bf16 and fp8 arrays hold
+    bit patterns (``is_fp8``; ``is_bf16`` or plain uint16 storage), every
+    other array its values."""
+    x = arr.array
+    if getattr(arr, "is_fp8", False):
+        return from_fp8_e4m3_bits(x)
+    return from_bf16_bits(x) if getattr(arr, "is_bf16", False) or x.dtype == np.uint16 else x
 
 
 def tile_coords(t: np.ndarray, M: int, N: int, BM: int, BN: int, group_m: int, panels: int = 0):
@@ -445,9 +508,8 @@ class GemmBf16:
         """Max relative error of sampled 256-row × 256-column blocks of
         :meth:`shells_result` against a float64 host product."""
         c = self.shells_result(panels)
-        a, b = self.A.array, self.B.array
-        a = (from_bf16_bits(a) if a.dtype == np.uint16 else a).reshape(self.M, self.K)
-        b = (from_bf16_bits(b) if b.dtype == np.uint16 else b).reshape(self.N, self.K)
+        a = decode_operand(self.A).reshape(self.M, self.K)
+        b = decode_operand(self.B).reshape(self.N, self.K)
         rng = np.random.default_rng(seed)
         worst = 0.0
         for _ in range(samples):
@@ -480,7 +542,10 @@ class GemmBf16:
 
         def operand(arr, rows):
             x = arr.array
-            if x.dtype == np.uint16:  # bf16 bit patterns
+            if getattr(arr, "is_fp8", False):
+                # e4m3fn bit patterns, decoded on the host (every e4m3 value is exact in bf16)
+                t = torch.from_numpy(x).view(torch.float8_e4m3fn).to(torch.bfloat16).to(device)
+            elif x.dtype == np.uint16:  # bf16 bit patterns
                 t = torch.from_numpy(x.view(np.int16)).to(device).view(torch.bfloat16)
             else:
                 t = torch.from_numpy(x).to(device)
@@ -535,10 +600,8 @@ class GemmBf16:
         ranges = self.cr.ranges(compute_id)
         refs = self.cr.references(compute_id)
         unit = self.L * self.split_k
-        a = from_bf16_bits(self.A.array).reshape(self.M, self.K) if self.A.array.dtype == np.uint16 else (
-            self.A.array.reshape(self.M, self.K))
-        b = from_bf16_bits(self.B.array).reshape(self.N, self.K) if self.B.array.dtype == np.uint16 else (
-            self.B.array.reshape(self.N, self.K))
+        a = decode_operand(self.A).reshape(self.M, self.K)
+        b = decode_operand(self.B).reshape(self.N, self.K)
         rng = np.random.default_rng(seed)
         saved = self.C.array.copy()
         worst = 0.0
@@ -632,8 +695,8 @@ class GemmBf16:
         self.C.array[lo:lo + n] = tmp[lo:lo + n]
 
     def reference(self, rows: slice = slice(None)) -> np.ndarray:
-        a = from_bf16_bits(self.A.array).reshape(self.M, self.K)[rows].astype(np.float64)
-        b = from_bf16_bits(self.B.array).reshape(self.N, self.K).astype(np.float64)
+        a = decode_operand(self.A).reshape(self.M, self.K)[rows].astype(np.float64)
+        b = decode_operand(self.B).reshape(self.N, self.K).astype(np.float64)
         return a @ b.T
 
 
@@ -681,3 +744,48 @@ class GemmF32(GemmBf16):
         a = self.A.array.reshape(self.M, self.K)[rows].astype(np.float64)
         b = self.B.array.reshape(self.N, self.K).astype(np.float64)
         return a @ b.T
+
+
+class GemmFp8(GemmBf16):
+    """``C = A · Bᵀ`` with OCP e4m3fn operands (one byte per element, half the
+    device memory and transfer bytes of bf16) and fp32 accumulation and
+    output: A ``[M][K]``, Bt ``[N][K]`` as ``ClArray(…, "float8_e4m3fn")``, C
+    tile-major in fragment order like :class:`GemmBf16`, so the range
+    partitioning, the streamed and shell paths and every ``verify`` apply
+    unchanged.  ``fill="random"`` draws uniform [−1, 1) values and quantises
+    them with :func:`to_fp8_e4m3_bits`.  K must be a multiple of 128."""
+
+    def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
+                 cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
+                 group_m: int = 4, wave_granularity: bool | None = None):
+        BM, BN, L, kname = FP8_TILES[tile]
+        self.tile = tile
+        if M % BM or N % BN or K % 128 or min(M, N, K) <= 0:
+            raise ValueError(f"M%{BM}, N%{BN} and K%128 must be 0 and M, N, K positive (got {M},{N},{K})")
+        self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
+        self.geom = FP8_TILE_WAVES[tile]  # C tiles in fragment order
+        self.row_major_c = False
+        self.exchange = False
+        self.exchange_shift = 0
+        self.split_k = 1
+        self.tiles = (M // BM) * (N // BN)
+        self.global_range = self.tiles * L
+        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_fp8"))
+        self.group_m = group_m
+        self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
+        self.dims.write = False
+        self.A = ClArray(M * K, "float8_e4m3fn")
+        self.B = ClArray(N * K, "float8_e4m3fn")
+        self.C = ClArray(M * N, np.float32)
+        for a in (self.A, self.B):
+            a.write = False
+        self.C.read = False
+        self.C.elements_per_work_item = BM * BN // L
+        self.extra = []
+        if fill == "random":
+            rng = np.random.default_rng(seed)
+            self.A.array[:] = to_fp8_e4m3_bits(rng.uniform(-1, 1, M * K).astype(np.float32))
+            self.B.array[:] = to_fp8_e4m3_bits(rng.uniform(-1, 1, N * K).astype(np.float32))
+        self._uploaded = False
+        self.wave_granularity = wave_granularity
+        self._orders = {}
