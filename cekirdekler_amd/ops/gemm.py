@@ -1,5 +1,6 @@
 """Range-partitioned GEMMs: bf16 (the "SGEMM 8192² bf16" config of
-BASELINE.json), fp32 on the fp32 matrix cores and fp8 (OCP e4m3fn).
+BASELINE.json), fp32 on the fp32 matrix cores, fp8 (OCP e4m3fn) and MXFP8
+(e4m3fn with one E8M0 scale per block of 32).
 
 ``C = A · Bᵀ`` with A ``[M][K]`` and Bt ``[N][K]`` bf16 row-major, C fp32 in
 tile-major layout (see ``kernels/sgemm_bf16.hip``).  The global range is one
@@ -144,6 +145,19 @@ FP8_TILES = {
 }
 FP8_TILE_WAVES = {"256x256pb": (2, 4, 8, 4), "256x256pbx": (2, 4, 8, 4), "128x128": (2, 2, 4, 4)}
 
+# MXFP8 tiles (kernels/sgemm_mxfp8.hip): the fp8 structures with E8M0 block
+# scales applied by v_mfma_scale_f32_16x16x128_f8f6f4.  Throughput beside the
+# unit-scale fp8 256x256pbx of the same run: profiles/gemm_mxfp8.md.
+MXFP8_TILES = {
+    # balanced-DMA ping-pong, packed scales global → VGPR one K-tile ahead:
+    # the GemmMxFp8 default
+    "256x256pbx": (256, 256, 512, "cek_sgemm_mxfp8_256x256pbx"),
+    # one LDS stage in flight, 4 waves: the simple kernel the other is judged against
+    "128x128": (128, 128, 256, "cek_sgemm_mxfp8_128x128"),
+}
+MXFP8_TILE_WAVES = {"256x256pbx": (2, 4, 8, 4), "128x128": (2, 2, 4, 4)}
+MX_BLOCK = 32  # elements per scale along K
+
 # tiles whose kernel stores C row-major ([M][N]) instead of tile-major
 ROW_MAJOR_TILES = {"256x256pbr"}
 # tiles with a split-K kernel variant ("<kernel>_sk", arrays + W + counters)
@@ -199,6 +213,69 @@ def to_fp8_e4m3_bits(x: np.ndarray) -> np.ndarray:
 def from_fp8_e4m3_bits(b: np.ndarray) -> np.ndarray:
     """OCP e4m3fn bit patterns (uint8) → fp32 (``0x7F`` / ``0xFF`` → NaN)."""
     return _FP8_E4M3[np.asarray(b, dtype=np.uint8)]
+
+
+def e8m0_to_f64(scales: np.ndarray) -> np.ndarray:
+    """E8M0 scale bytes → float64 ``2^(byte − 127)``, exact (``0xFF`` → NaN)."""
+    s = np.asarray(scales, dtype=np.uint8)
+    return np.where(s == 0xFF, np.nan, np.ldexp(1.0, s.astype(np.int64) - 127))
+
+
+def to_mxfp8(x: np.ndarray, block: int = MX_BLOCK):
+    """OCP Microscaling (MX v1.0) MXFP8 along the last axis: ``(codes uint8
+    [..., K], scales uint8 [..., K/block])``.  Per block the shared exponent is
+    ``e = floor(log2(max |x| over the block's finite values)) − 8`` (8: the
+    exponent of e4m3's largest binade), clamped to [−127, 127], the scale byte
+    ``e + 127`` and the elements ``to_fp8_e4m3_bits(x · 2^−e)``: round to
+    nearest even, saturating, so scaled values in (448, 512) become ±448.  A
+    block without a finite nonzero value gets byte 127; NaN → ``0x7F`` without
+    a say in the scale; ±inf → ±448.  ``0xFF`` (E8M0 NaN) is never produced.
+    ``x`` is taken as float32 (float64 is kept for the scale and the scaling,
+    the element rounding then goes through float32)."""
+    x = np.asarray(x)
+    x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+    K = x.shape[-1]
+    if block <= 0 or K % block:
+        raise ValueError(f"the last axis ({K}) must be a multiple of the block ({block})")
+    xb = x.reshape(x.shape[:-1] + (K // block, block)).astype(np.float64)
+    amax = np.where(np.isfinite(xb), np.abs(xb), 0.0).max(axis=-1)
+    _, ex = np.frexp(amax)  # amax = m · 2^ex, 0.5 <= m < 1: floor(log2 amax) = ex − 1
+    e = np.clip(np.where(amax > 0, ex.astype(np.int64) - 9, 0), -127, 127)
+    with np.errstate(over="ignore", invalid="ignore"):
+        scaled = np.ldexp(xb, -e[..., None]).astype(np.float32)
+    return to_fp8_e4m3_bits(scaled).reshape(x.shape), (e + 127).astype(np.uint8)
+
+
+def from_mxfp8(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """MXFP8 → float32: ``e4m3(code) · 2^(scale − 127)`` with one scale per
+    ``K / scales.shape[-1]`` elements of the last axis.  (The product is taken
+    in float64; what float32 cannot hold rounds, overflows or underflows.)"""
+    codes, scales = np.asarray(codes, np.uint8), np.asarray(scales, np.uint8)
+    nb = scales.shape[-1]
+    v = from_fp8_e4m3_bits(codes).astype(np.float64).reshape(scales.shape + (codes.shape[-1] // nb,))
+    with np.errstate(over="ignore", invalid="ignore"):
+        return (v * e8m0_to_f64(scales)[..., None]).astype(np.float32).reshape(codes.shape)
+
+
+def pack_mx_scales(s: np.ndarray) -> np.ndarray:
+    """Row-major scale bytes ``[R][K/32]`` → the kernels' packed dwords
+    (kernels/sgemm_mxfp8.hip): uint32 ``[K/128][R/64][64]``, byte ``i`` of
+    dword ``(kt·R/64 + g)·64 + l`` = ``s[g·64 + i·16 + l % 16][kt·4 + l // 16]``.
+    R % 64 = 0 and (K/32) % 4 = 0."""
+    s = np.asarray(s, np.uint8)
+    R, nb = s.shape
+    if R % 64 or nb % 4:
+        raise ValueError(f"rows % 64 and blocks % 4 must be 0 (got {R}, {nb})")
+    x = s.reshape(R // 64, 4, 16, nb // 4, 4)  # g i fr kt fq
+    return np.ascontiguousarray(x.transpose(3, 0, 4, 2, 1)).view("<u4").reshape(nb // 4, R // 64, 64)  # kt g fq fr [i]
+
+
+def unpack_mx_scales(p: np.ndarray) -> np.ndarray:
+    """Inverse of :func:`pack_mx_scales`: uint32 ``[K/128][R/64][64]`` → uint8 ``[R][K/32]``."""
+    p = np.ascontiguousarray(p, dtype="<u4")
+    KT, G, _ = p.shape
+    x = p.view(np.uint8).reshape(KT, G, 4, 16, 4)  # kt g fq fr i
+    return np.ascontiguousarray(x.transpose(1, 4, 3, 0, 2)).reshape(G * 64, KT * 4)  # g i fr kt fq
 
 
 def decode_operand(arr: ClArray) -> np.ndarray:
@@ -394,7 +471,7 @@ class GemmBf16:
         if streamed and not self.can_stream():
             raise ValueError("stream_blobs needs split_k == 1, whole tile groups and an integral A panel "
                              "per work item")
-        for a in (self.dims, self.A, self.B):
+        for a in self._inputs(first or not resident):
             a.read = first or not resident
         self.A.partial_read = streamed
         # an A row panel of one tile group spans group_m·BM rows; per work item
@@ -405,11 +482,40 @@ class GemmBf16:
         gran = self.granularity()
         if streamed:
             gran = self._group_work_items()
-        self.dims.next_param(self.A, self.B, self.C, *self.extra).compute(
+        self.dims.next_param(*self._params()).compute(
             self.cr, compute_id, self.kernel, self.global_range, self.L,
             pipeline=streamed, pipeline_type=stream_event, pipeline_blobs=max(1, stream_blobs),
             granularity=gran)
         self._uploaded = True
+
+    def _inputs(self, upload: bool) -> tuple:
+        """The arrays a call reads (``upload``: this call sends them to the devices)."""
+        return self.dims, self.A, self.B
+
+    def _params(self) -> tuple:
+        """The kernel's array parameters after ``dims``, in its order."""
+        return (self.A, self.B, self.C, *self.extra)
+
+    def _operand(self, name: str) -> np.ndarray:
+        """Operand ``"A"`` (``[M][K]``) or ``"B"`` (``[N][K]``) as the numbers
+        the kernel multiplies: what every host reference is computed from."""
+        arr, rows = (self.A, self.M) if name == "A" else (self.B, self.N)
+        return decode_operand(arr).reshape(rows, self.K)
+
+    def _operand_t(self, name: str, device):
+        """:meth:`_operand` as a float64 torch tensor on ``device``."""
+        import torch
+
+        arr, rows = (self.A, self.M) if name == "A" else (self.B, self.N)
+        x = arr.array
+        if getattr(arr, "is_fp8", False):
+            # e4m3fn bit patterns, decoded on the host (every e4m3 value is exact in bf16)
+            t = torch.from_numpy(x).view(torch.float8_e4m3fn).to(torch.bfloat16).to(device)
+        elif x.dtype == np.uint16:  # bf16 bit patterns
+            t = torch.from_numpy(x.view(np.int16)).to(device).view(torch.bfloat16)
+        else:
+            t = torch.from_numpy(x).to(device)
+        return t.reshape(rows, self.K).double()
 
     def shell_bounds(self, panels: int, split_last: int = 0):
         """Work-item bounds of the square shells (blob s = shell s) and the
@@ -508,8 +614,8 @@ class GemmBf16:
         """Max relative error of sampled 256-row × 256-column blocks of
         :meth:`shells_result` against a float64 host product."""
         c = self.shells_result(panels)
-        a = decode_operand(self.A).reshape(self.M, self.K)
-        b = decode_operand(self.B).reshape(self.N, self.K)
+        a = self._operand("A")
+        b = self._operand("B")
         rng = np.random.default_rng(seed)
         worst = 0.0
         for _ in range(samples):
@@ -538,20 +644,7 @@ class GemmBf16:
 
     def _reference_t(self, device):
         """C = A·Bᵀ in float64 on a torch device (row-major [M][N])."""
-        import torch
-
-        def operand(arr, rows):
-            x = arr.array
-            if getattr(arr, "is_fp8", False):
-                # e4m3fn bit patterns, decoded on the host (every e4m3 value is exact in bf16)
-                t = torch.from_numpy(x).view(torch.float8_e4m3fn).to(torch.bfloat16).to(device)
-            elif x.dtype == np.uint16:  # bf16 bit patterns
-                t = torch.from_numpy(x.view(np.int16)).to(device).view(torch.bfloat16)
-            else:
-                t = torch.from_numpy(x).to(device)
-            return t.reshape(rows, self.K).double()
-
-        return operand(self.A, self.M) @ operand(self.B, self.N).T
+        return self._operand_t("A", device) @ self._operand_t("B", device).T
 
     def result(self, download: bool = True) -> np.ndarray:
         """Row-major fp32 C (downloads every device's slice when resident)."""
@@ -600,8 +693,8 @@ class GemmBf16:
         ranges = self.cr.ranges(compute_id)
         refs = self.cr.references(compute_id)
         unit = self.L * self.split_k
-        a = decode_operand(self.A).reshape(self.M, self.K)
-        b = decode_operand(self.B).reshape(self.N, self.K)
+        a = self._operand("A")
+        b = self._operand("B")
         rng = np.random.default_rng(seed)
         saved = self.C.array.copy()
         worst = 0.0
@@ -695,8 +788,8 @@ class GemmBf16:
         self.C.array[lo:lo + n] = tmp[lo:lo + n]
 
     def reference(self, rows: slice = slice(None)) -> np.ndarray:
-        a = decode_operand(self.A).reshape(self.M, self.K)[rows].astype(np.float64)
-        b = decode_operand(self.B).reshape(self.N, self.K).astype(np.float64)
+        a = self._operand("A")[rows].astype(np.float64)
+        b = self._operand("B").astype(np.float64)
         return a @ b.T
 
 
@@ -789,3 +882,98 @@ class GemmFp8(GemmBf16):
         self._uploaded = False
         self.wave_granularity = wave_granularity
         self._orders = {}
+
+
+class GemmMxFp8(GemmBf16):
+    """``C = (A∘SA) · (B∘SB)ᵀ`` in OCP MXFP8: e4m3fn elements (``A``, ``B`` as
+    in :class:`GemmFp8`) with one E8M0 scale byte per 32 consecutive k, an
+    element's value being ``e4m3(code) · 2^(scale − 127)``; fp32 accumulation
+    and output, C tile-major in fragment order like :class:`GemmBf16`.
+
+    ``SA`` (``M·K/32``) and ``SB`` (``N·K/32``) are the row-major uint8 scale
+    arrays a user fills (:func:`to_mxfp8` produces codes and scales).  The
+    kernels read them in a packed layout (:func:`pack_mx_scales`), kept in
+    device-side arrays of this object and re-packed from ``SA`` / ``SB``
+    whenever the operands are uploaded: on the first call, and on every
+    ``resident=False`` call.  On several devices, and in streamed calls, the
+    scale arrays go whole to every device.
+
+    ``fill="random"`` draws uniform [−1, 1) values times ``2^u`` per block, u
+    an integer uniform in [−12, 12], and quantises them with
+    :func:`to_mxfp8`.  K must be a multiple of 128.  The shell paths are not
+    available."""
+
+    def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
+                 cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
+                 group_m: int = 4, wave_granularity: bool | None = None):
+        BM, BN, L, kname = MXFP8_TILES[tile]
+        self.tile = tile
+        if M % BM or N % BN or K % 128 or min(M, N, K) <= 0:
+            raise ValueError(f"M%{BM}, N%{BN} and K%128 must be 0 and M, N, K positive (got {M},{N},{K})")
+        self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
+        self.geom = MXFP8_TILE_WAVES[tile]  # C tiles in fragment order
+        self.row_major_c = False
+        self.exchange = False
+        self.exchange_shift = 0
+        self.split_k = 1
+        self.tiles = (M // BM) * (N // BN)
+        self.global_range = self.tiles * L
+        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_mxfp8"))
+        self.group_m = group_m
+        self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
+        self.dims.write = False
+        self.A = ClArray(M * K, "float8_e4m3fn")
+        self.B = ClArray(N * K, "float8_e4m3fn")
+        self.SA = ClArray(np.full(M * K // MX_BLOCK, 127, np.uint8))  # 2^0
+        self.SB = ClArray(np.full(N * K // MX_BLOCK, 127, np.uint8))
+        # the packed scales the kernels read; run() fills them from SA / SB
+        self._SAp = ClArray(np.zeros(M * K // 128, np.uint32))
+        self._SBp = ClArray(np.zeros(N * K // 128, np.uint32))
+        self.C = ClArray(M * N, np.float32)
+        for a in (self.A, self.B, self._SAp, self._SBp):
+            a.write = False
+        self.C.read = False
+        self.C.elements_per_work_item = BM * BN // L
+        self.extra = []
+        if fill == "random":
+            rng = np.random.default_rng(seed)
+            for arr, sc, rows in ((self.A, self.SA, M), (self.B, self.SB, N)):
+                x = rng.uniform(-1, 1, (rows, K // MX_BLOCK, MX_BLOCK))
+                x = np.ldexp(x, rng.integers(-12, 13, (rows, K // MX_BLOCK, 1)))
+                codes, scales = to_mxfp8(x.astype(np.float32).reshape(rows, K))
+                arr.array[:] = codes.ravel()
+                sc.array[:] = scales.ravel()
+        self._uploaded = False
+        self.wave_granularity = wave_granularity
+        self._orders = {}
+
+    def _inputs(self, upload: bool) -> tuple:
+        if upload:  # the operands go up: the packed scales follow the public ones
+            self._SAp.array[:] = pack_mx_scales(self.SA.array.reshape(self.M, -1)).ravel()
+            self._SBp.array[:] = pack_mx_scales(self.SB.array.reshape(self.N, -1)).ravel()
+        return self.dims, self.A, self.B, self._SAp, self._SBp
+
+    def _params(self) -> tuple:
+        return self.A, self.B, self._SAp, self._SBp, self.C
+
+    def _scales(self, name: str) -> np.ndarray:
+        """float64 ``[rows][K/32]`` scale factors of operand ``name``."""
+        arr, rows = (self.SA, self.M) if name == "A" else (self.SB, self.N)
+        return e8m0_to_f64(arr.array.reshape(rows, self.K // MX_BLOCK))
+
+    def _operand(self, name: str) -> np.ndarray:
+        """Dequantised operand, float64 (the product with the scale is exact there)."""
+        x = super()._operand(name).astype(np.float64)
+        return (x.reshape(-1, self.K // MX_BLOCK, MX_BLOCK) * self._scales(name)[..., None]).reshape(-1, self.K)
+
+    def _operand_t(self, name: str, device):
+        import torch
+
+        x = super()._operand_t(name, device)
+        sc = torch.from_numpy(self._scales(name)).to(device)
+        return (x.view(-1, self.K // MX_BLOCK, MX_BLOCK) * sc[..., None]).view(-1, self.K)
+
+    def _no_shells(self, *a, **k):
+        raise NotImplementedError("GemmMxFp8 has no shell paths: the shell streamer (csrc/shell_gemm.cpp) passes no scales")
+
+    run_shells = run_host_shells = verify_shells = verify_shells_full = _no_shells

@@ -28,6 +28,7 @@ LIBRARY = {
                   "cek_sgemm_f32_256x256g8i", "cek_sgemm_f32_256x256g8h",
                   "cek_sgemm_f32_256x256g8q"],
     "sgemm_fp8": ["cek_sgemm_fp8_128x128", "cek_sgemm_fp8_256x256pb", "cek_sgemm_fp8_256x256pbx"],
+    "sgemm_mxfp8": ["cek_sgemm_mxfp8_128x128", "cek_sgemm_mxfp8_256x256pbx"],
     "mandelbrot": ["cek_mandelbrot_f32", "cek_mandelbrot_blk8_f32", "cek_mandelbrot_blk8h_f32",
                    "cek_mandelbrot_blk8k_f32", "cek_mandelbrot_blk8m_f32", "cek_mandelbrot_blk8t_f32",
                    "cek_mandelbrot_blk8u_f32", "cek_mandelbrot_blk8r_f32",
@@ -45,6 +46,7 @@ ARITY = {
     **{k: (6 if k.endswith(("_sk", "_sw", "_sh", "_ss")) else 4) for k in LIBRARY["sgemm_bf16"]},
     **{k: 4 for k in LIBRARY["sgemm_f32"]},
     **{k: 4 for k in LIBRARY["sgemm_fp8"]},
+    **{k: 6 for k in LIBRARY["sgemm_mxfp8"]},  # dims, A, Bt, packed SA, packed SB, C
     **{k: 3 for k in LIBRARY["mandelbrot"]},
     **{k: 4 for k in LIBRARY["nbody"] if "energy" not in k},
     **{k: 3 for k in LIBRARY["nbody"] if "energy" in k},
