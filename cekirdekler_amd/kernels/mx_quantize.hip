@@ -1,0 +1,182 @@
+// MXFP8 quantisation on the device (HBM-bound): fp32 or bf16 in, OCP e4m3fn
+// codes plus one E8M0 scale byte per block of 32 consecutive elements out,
+// bit for bit what ops/gemm.py's to_mxfp8 computes, and the repack of the
+// row-major scale bytes into the dwords the MXFP8 GEMM kernels read
+// (sgemm_mxfp8.hip, pack_mx_scales).
+//
+// Quantise: work item i owns MX block i, the local size is 64, so a
+// work-group (one wave) owns 64 consecutive blocks = 2048 elements.  LPB
+// lanes share a block (fp32: 8 lanes × float4, bf16: 4 lanes × 8 values; 16 B
+// per lane either way), so one step of the wave reads 1 KiB contiguous and
+// covers 64 / LPB blocks, and LPB steps cover the group.  All loads are issued
+// before the first use.
+//
+// Per step the block maximum of the finite |x| is taken on the bit patterns
+// (integer max: nothing is flushed or canonicalised) with DPP inside the LPB
+// lanes, and the scale byte comes from its exponent field.  The elements are
+// scaled and rounded by v_cvt_scalef32_pk_fp8_f32 (two values per
+// instruction, the scale operand 2^e given by its exponent field alone, so
+// e = -127 is field 0 and fp32 denormal inputs are scaled exactly).  Measured
+// against the host codec on every designed pattern (profiles/quantize_mxfp8.md)
+// the instruction rounds to nearest even exactly like the codec, subnormals
+// included, and differs in two places: what rounds past 448 (and inf) becomes
+// a NaN code where the codec saturates to ±448, and a NaN keeps a sign where
+// the codec writes 0x7f.  Both are put right on the packed dword with the
+// per-element NaN bits of the input (mxq_fix).
+//
+// A lane stores its codes as one dword (fp32) or two (bf16); the group's 64
+// scale bytes are collected with four ds_bpermute into lanes 0..15 and stored
+// as 16 dwords.  No LDS.
+//
+// Pack: work item i writes packed dword i = (kt·R/64 + g)·64 + l, whose byte b
+// is S[g·64 + b·16 + l % 16][kt·4 + l / 16].  Lane l loads the dword
+// S[g·64 + l][kt·4 .. kt·4 + 3]; four ds_bpermute transpose the 64 × 4 bytes.
+#include "cek_kernel.h"
+
+typedef unsigned int u32;
+typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float mxq_float(u32 u) { return __builtin_bit_cast(float, u); }
+
+// |x| bits + 2^23 as a signed int: finite values stay positive and keep their
+// order, inf is INT_MIN and NaN lies above it, so a signed max is the maximum
+// over the finite values wherever there is one
+__device__ __forceinline__ int mxq_key(u32 u) { return (int)((u & 0x7fffffffu) + 0x00800000u); }
+
+// 0x80 in byte `k` for the key of a NaN, else 0
+__device__ __forceinline__ u32 mxq_nan_bit(int key, int k) {
+  return (u32)((int)(0x80000000u - (u32)key) >> 31) & (0x80u << (8 * k));
+}
+
+// max over the LPB lanes of a block (LPB-aligned lane groups), in every lane
+template <int LPB>
+__device__ __forceinline__ int mxq_block_max(int m) {
+  // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror (lane i <-> 7 - i
+  // of each 8, equal quads by then)
+  m = max(m, __builtin_amdgcn_update_dpp(0, m, 0xB1, 0xF, 0xF, true));
+  m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x4E, 0xF, 0xF, true));
+  if (LPB == 8) m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x141, 0xF, 0xF, true));
+  return m;
+}
+
+// scale byte e + 127 from a block's maximum key: e = max(E - 135, -127) with E
+// the exponent field of the finite |x| maximum, e = 0 when that is 0 or no
+// element is finite
+__device__ __forceinline__ u32 mxq_scale_byte(int key) {
+  const u32 amax = (u32)max(key, 0x00800000) - 0x00800000u;
+  return amax == 0u ? 127u : (u32)max((int)(amax >> 23) - 8, 0);
+}
+
+// The conversion's dword made the codec's.  Bytes whose low seven bits are all
+// ones came from a NaN (`nan`: 0x80 in that byte) or from a value that rounded
+// past 448: the latter become 0x7e under their sign, a NaN loses its sign.
+__device__ __forceinline__ u32 mxq_fix(u32 w, u32 nan) {
+  const u32 full = ((w & 0x7f7f7f7fu) + 0x01010101u) & 0x80808080u;
+  return (w - ((full & ~nan) >> 7)) & ~nan;
+}
+
+// four values scaled by 2^-e (`scale` = 2^e) and rounded to e4m3fn
+__device__ __forceinline__ u32 mxq_cvt4(float a, float b, float c, float d, float scale) {
+  s16x2 r = {0, 0};
+  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, a, b, scale, false);
+  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, c, d, scale, true);
+  return __builtin_bit_cast(u32, r);
+}
+
+// The group's 64 scale bytes as 16 dwords.  `mine` is, in every lane, the
+// scale byte of the block this lane's group had in step (lane % LPB).  Dword
+// j, byte b is block 4j + b: step (4j + b) / GPS, lane group (4j + b) % GPS,
+// GPS = 64 / LPB groups per step.
+template <int LPB>
+__device__ __forceinline__ void mxq_store_scales(u32 mine, u32* scales32, long long group, int lane) {
+  constexpr int GPS = 64 / LPB;
+  const int j = lane & 15;
+  u32 w = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int blk = 4 * j + b, src = (blk % GPS) * LPB + blk / GPS;
+    w |= (u32)__builtin_amdgcn_ds_bpermute(src << 2, (int)mine) << (8 * b);
+  }
+  if (lane < 16) scales32[group * 16 + lane] = w;
+}
+
+extern "C" __global__ __launch_bounds__(64) void cek_mx_quantize_f32(const u32x4* x, u32* codes, u32* scales,
+                                                                      CEK_HIDDEN) {
+  const int lane = (int)threadIdx.x;
+  const long long group = cek_global_group_id();
+  if (group * 64 >= __cek_gsize) return;
+  const long long base = group * 512 + lane;  // in units of 4 elements
+  u32x4 v[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) v[s] = x[base + s * 64];
+  u32 mine = 0;
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const int k0 = mxq_key(v[s].x), k1 = mxq_key(v[s].y), k2 = mxq_key(v[s].z), k3 = mxq_key(v[s].w);
+    const u32 sb = mxq_scale_byte(mxq_block_max<8>(max(max(k0, k1), max(k2, k3))));
+    const u32 nan = mxq_nan_bit(k0, 0) | mxq_nan_bit(k1, 1) | mxq_nan_bit(k2, 2) | mxq_nan_bit(k3, 3);
+    const float scale = mxq_float(sb << 23);  // 2^e, e = sb - 127
+    codes[base + s * 64] = mxq_fix(
+        mxq_cvt4(mxq_float(v[s].x), mxq_float(v[s].y), mxq_float(v[s].z), mxq_float(v[s].w), scale), nan);
+    mine = (lane & 7) == s ? sb : mine;
+  }
+  mxq_store_scales<8>(mine, scales, group, lane);
+}
+
+extern "C" __global__ __launch_bounds__(64) void cek_mx_quantize_bf16(const u32x4* x, u32x2* codes, u32* scales,
+                                                                       CEK_HIDDEN) {
+  const int lane = (int)threadIdx.x;
+  const long long group = cek_global_group_id();
+  if (group * 64 >= __cek_gsize) return;
+  const long long base = group * 256 + lane;  // in units of 8 elements
+  u32x4 v[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) v[s] = x[base + s * 64];
+  u32 mine = 0;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    u32 f[8];  // bf16 bit patterns are the high halves of fp32's
+    int m = 0;
+    u32x2 nan = {0, 0};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      f[2 * q] = v[s][q] << 16;
+      f[2 * q + 1] = v[s][q] & 0xffff0000u;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int key = mxq_key(f[i]);
+      m = max(m, key);
+      nan[i >> 2] |= mxq_nan_bit(key, i & 3);
+    }
+    const u32 sb = mxq_scale_byte(mxq_block_max<4>(m));
+    const float scale = mxq_float(sb << 23);
+    u32x2 c;
+    c.x = mxq_fix(mxq_cvt4(mxq_float(f[0]), mxq_float(f[1]), mxq_float(f[2]), mxq_float(f[3]), scale), nan.x);
+    c.y = mxq_fix(mxq_cvt4(mxq_float(f[4]), mxq_float(f[5]), mxq_float(f[6]), mxq_float(f[7]), scale), nan.y);
+    codes[base + s * 64] = c;
+    mine = (lane & 3) == s ? sb : mine;
+  }
+  mxq_store_scales<4>(mine, scales, group, lane);
+}
+
+// dims = {R, K}; S row-major [R][K/32] read as dwords [R][K/128]; P [K/128][R/64][64]
+extern "C" __global__ __launch_bounds__(64) void cek_mx_pack_scales(const int* dims, const u32* s, u32* p,
+                                                                     CEK_HIDDEN) {
+  const int lane = (int)threadIdx.x;
+  const long long t = cek_global_group_id();  // kt · R/64 + g
+  const long long G = dims[0] / 64, KT = dims[1] / 128;
+  if (t * 64 >= __cek_gsize || t >= KT * G) return;
+  const u32 kt = (u32)t / (u32)G, g = (u32)t % (u32)G;  // t < KT·G = R·K / 8192 fits 32 bits
+  const u32 mine = s[((long long)g * 64 + lane) * KT + kt];  // row g·64 + lane, blocks kt·4 .. kt·4 + 3
+  const int fr = lane & 15, fq = lane >> 4;
+  u32 w = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const u32 row = (u32)__builtin_amdgcn_ds_bpermute((b * 16 + fr) << 2, (int)mine);
+    w |= ((row >> (8 * fq)) & 0xffu) << (8 * b);
+  }
+  p[t * 64 + lane] = w;
+}

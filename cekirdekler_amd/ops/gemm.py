@@ -901,7 +901,14 @@ class GemmMxFp8(GemmBf16):
     ``fill="random"`` draws uniform [−1, 1) values times ``2^u`` per block, u
     an integer uniform in [−12, 12], and quantises them with
     :func:`to_mxfp8`.  K must be a multiple of 128.  The shell paths are not
-    available."""
+    available.
+
+    :meth:`quantize` makes an operand from fp32 or bf16 data on the devices
+    instead (``kernels/mx_quantize.hip``, the same bits as :func:`to_mxfp8`):
+    codes, scales and packed scales stay resident and the next resident
+    :meth:`run` uploads nothing for that operand; its host arrays are stale
+    until :meth:`sync_operands`, which every host reference (``verify*``,
+    ``reference``) calls first."""
 
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
@@ -918,7 +925,9 @@ class GemmMxFp8(GemmBf16):
         self.split_k = 1
         self.tiles = (M // BM) * (N // BN)
         self.global_range = self.tiles * L
-        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_mxfp8"))
+        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_mxfp8", "mx_quantize"))
+        self._stale = set()  # operands quantised on the device whose host arrays are behind
+        self._quantizers = {}
         self.group_m = group_m
         self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
         self.dims.write = False
@@ -948,27 +957,115 @@ class GemmMxFp8(GemmBf16):
         self._orders = {}
 
     def _inputs(self, upload: bool) -> tuple:
+        # an operand quantised on the device is resident with its packed
+        # scales: it is neither uploaded nor re-packed from its (stale) host arrays
+        host = [n for n in ("A", "B") if n not in self._stale]
         if upload:  # the operands go up: the packed scales follow the public ones
-            self._SAp.array[:] = pack_mx_scales(self.SA.array.reshape(self.M, -1)).ravel()
-            self._SBp.array[:] = pack_mx_scales(self.SB.array.reshape(self.N, -1)).ravel()
-        return self.dims, self.A, self.B, self._SAp, self._SBp
+            if "A" in host:
+                self._SAp.array[:] = pack_mx_scales(self.SA.array.reshape(self.M, -1)).ravel()
+            if "B" in host:
+                self._SBp.array[:] = pack_mx_scales(self.SB.array.reshape(self.N, -1)).ravel()
+        trio = {"A": (self.A, self._SAp), "B": (self.B, self._SBp)}
+        return (self.dims, *(trio[n][0] for n in host), *(trio[n][1] for n in host))
 
     def _params(self) -> tuple:
         return self.A, self.B, self._SAp, self._SBp, self.C
 
+    def run(self, compute_id: int = 1, resident: bool = True, stream_blobs: int = 0,
+            stream_event: bool = True) -> None:
+        """:meth:`GemmBf16.run`.  An operand quantised on the device
+        (:meth:`quantize`) is used where it lies: a resident call uploads only
+        the other operand (on its first call) and ``dims``; a host-resident
+        call would send the stale host arrays and is refused until
+        :meth:`sync_operands` has fetched them."""
+        if self._stale and not resident:
+            raise ValueError(f"operand(s) {sorted(self._stale)} were quantised on the device and the host arrays are "
+                             "stale: call sync_operands() before a run(resident=False)")
+        super().run(compute_id, resident, stream_blobs, stream_event)
+
+    def quantize(self, name: str, x, src: str | None = None, download: bool = False) -> None:
+        """Quantise operand ``name`` (``"A"``: ``[M][K]``, ``"B"``: ``[N][K]``)
+        to MXFP8 on the devices of this GEMM's cruncher
+        (:class:`~cekirdekler_amd.ops.quantize.MxFp8Quantizer`, bit for bit
+        :func:`to_mxfp8`): afterwards the codes, the row-major scales and the
+        packed scales are resident on every device and the next resident
+        :meth:`run` uses them without an upload.
+
+        ``x``: a float32 numpy array (copied into a pinned array of this
+        object and uploaded), bf16 bit patterns as a uint16 numpy array with
+        ``src="bfloat16"``, or a float32 / bf16 :class:`ClArray`, whose
+        ``read`` flag says whether it is uploaded (``False``: it is resident,
+        e.g. another kernel of this cruncher wrote it).  ``download=True``
+        also brings the codes and scales into ``A`` / ``SA`` (``B`` / ``SB``);
+        otherwise the host arrays are stale until :meth:`sync_operands`."""
+        from .quantize import MxFp8Quantizer, _src_name
+
+        if name not in ("A", "B"):
+            raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
+        rows = self.M if name == "A" else self.N
+        n = rows * self.K
+        if isinstance(x, ClArray):
+            given = "bfloat16" if x.is_bf16 else "float32" if x.array.dtype == np.float32 else None
+            if given is None or (src is not None and _src_name(src) != given):
+                raise ValueError(f"x must be a float32 or bfloat16 ClArray matching src (got {x.dtype_name}, src={src!r})")
+            length, key, upload = x.N, (name, given, x.uid), x.read
+        else:
+            given = _src_name(src or "float32")
+            x = np.asarray(x)
+            if given == "bfloat16" and x.dtype != np.uint16:
+                raise ValueError("a bfloat16 operand is given as uint16 bit patterns or as a bf16 ClArray")
+            if given == "float32" and x.dtype != np.float32:
+                raise ValueError(f"a float32 operand is given as a float32 array (got {x.dtype})")
+            length, key, upload = x.size, (name, given, None), True
+        if length != n:
+            raise ValueError(f"operand {name} has {rows}x{self.K} = {n} elements (got {length})")
+        q = self._quantizers.get(key)
+        if q is None:
+            for k in [k for k in self._quantizers if k[0] == name]:  # one quantizer (and input buffer) per operand
+                del self._quantizers[k]
+            codes, scales, packed = (self.A, self.SA, self._SAp) if name == "A" else (self.B, self.SB, self._SBp)
+            q = MxFp8Quantizer(rows, self.K, given, cruncher=self.cr, codes=codes, scales=scales, packed=packed,
+                               x=x if isinstance(x, ClArray) else None)
+            self._quantizers[key] = q
+        if not isinstance(x, ClArray):
+            q.X.array[:] = x.reshape(-1)
+        base = 0x4D58 + (0 if name == "A" else 2)  # compute ids of the quantise and pack computes
+        q.run(compute_id=base, upload=upload, download=download, pack_compute_id=base + 1)
+        for a in (q.codes, q.scales, q.packed):
+            a.read = False  # resident: the next run() must not send the host copy
+        if download:
+            self._stale.discard(name)
+        else:
+            self._stale.add(name)
+
+    def sync_operands(self) -> None:
+        """Download the codes and row-major scales of every operand quantised
+        on the device (from device 0, which holds them whole) into ``A`` /
+        ``SA`` / ``B`` / ``SB`` and clear their stale mark."""
+        for name in sorted(self._stale):
+            for a in ((self.A, self.SA) if name == "A" else (self.B, self.SB)):
+                self.cr.download(a, 0)
+        self._stale.clear()
+
     def _scales(self, name: str) -> np.ndarray:
         """float64 ``[rows][K/32]`` scale factors of operand ``name``."""
+        if self._stale:
+            self.sync_operands()
         arr, rows = (self.SA, self.M) if name == "A" else (self.SB, self.N)
         return e8m0_to_f64(arr.array.reshape(rows, self.K // MX_BLOCK))
 
     def _operand(self, name: str) -> np.ndarray:
         """Dequantised operand, float64 (the product with the scale is exact there)."""
+        if self._stale:
+            self.sync_operands()
         x = super()._operand(name).astype(np.float64)
         return (x.reshape(-1, self.K // MX_BLOCK, MX_BLOCK) * self._scales(name)[..., None]).reshape(-1, self.K)
 
     def _operand_t(self, name: str, device):
         import torch
 
+        if self._stale:
+            self.sync_operands()
         x = super()._operand_t(name, device)
         sc = torch.from_numpy(self._scales(name)).to(device)
         return (x.view(-1, self.K // MX_BLOCK, MX_BLOCK) * sc[..., None]).view(-1, self.K)

@@ -1,0 +1,197 @@
+"""MXFP8 quantisation on the device (``kernels/mx_quantize.hip``): fp32 or
+bf16 in device memory in, OCP e4m3fn codes plus one E8M0 scale byte per block
+of 32 out, and the scales once more in the packed layout the MXFP8 GEMM
+kernels read.  The result is :func:`cekirdekler_amd.ops.gemm.to_mxfp8`'s bit
+for bit (:func:`mxfp8_reference`); :func:`mxfp8_kernel_model` is the kernels'
+algorithm in integer and float32 numpy operations, the executable
+specification the host tests hold against the float64 codec.
+
+The input is ``[rows][K]`` row-major with K % 32 = 0, so it is a flat
+sequence of ``rows·K/32`` blocks and work item i owns block i: the quantise
+compute is range-partitioned by blocks (local size 64, a work-group owns 2048
+consecutive elements), every device's slice of the codes and of the row-major
+scales is contiguous, and on several devices both are gathered device to
+device so that every replica is whole.  The packed layout is K-tile-major,
+not contiguous per row slice: a second compute (one work item per packed
+dword) builds it from the whole row-major scales.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ..arrays import ClArray
+from ..cruncher import ClComputeError, ClNumberCruncher
+from .gemm import MX_BLOCK, from_bf16_bits, to_mxfp8
+from .library import LIBRARY, library
+
+QUANTIZE_KERNELS = {"float32": "cek_mx_quantize_f32", "bfloat16": "cek_mx_quantize_bf16"}
+PACK_KERNEL = "cek_mx_pack_scales"
+LOCAL = 64  # work items (= blocks) per work-group
+_SRC_NAMES = {"float32": "float32", "float": "float32", "f32": "float32", "bfloat16": "bfloat16", "bf16": "bfloat16"}
+
+
+def _src_name(src) -> str:
+    key = _SRC_NAMES.get(src.lower()) if isinstance(src, str) else None
+    if key is None:
+        raise ValueError(f"src must be 'float32' or 'bfloat16' (got {src!r})")
+    return key
+
+
+def mxfp8_reference(x) -> tuple:
+    """What the quantise kernels compute: :func:`to_mxfp8` of the float32
+    input, or of the decoded values of bf16 bit patterns (a uint16 array or a
+    bf16 :class:`ClArray`): ``(codes, scales)``, blocks along the last axis."""
+    if isinstance(x, ClArray):
+        x = x.array
+    x = np.asarray(x)
+    return to_mxfp8(from_bf16_bits(x) if x.dtype == np.uint16 else x.astype(np.float32, copy=False))
+
+
+def e4m3_convert_model(y: np.ndarray) -> np.ndarray:
+    """gfx950's fp8 conversion of float32 ``y`` as the GPU tier found it
+    (profiles/quantize_mxfp8.md), uint32 codes under the sign of ``y``: round
+    to nearest even at 3 mantissa bits, below 2^-6 in units of 2^-9 (the bit
+    rounding of ``aux_functions.py``'s ``cek_f32_to_fp8_e4m3``), and whatever
+    rounds past 448, inf and NaN as the all-ones code 0x7f."""
+    u = np.ascontiguousarray(y, np.float32).view(np.uint32)
+    a = u & np.uint32(0x7FFFFFFF)
+    s = (u >> np.uint32(24)) & np.uint32(0x80)
+    c = np.minimum(a, np.uint32(0x43F00000))  # 480, where 0x7f would lie: the normal path gives 0x7f
+    norm = ((c + np.uint32(0x7FFFF) + ((c >> np.uint32(20)) & np.uint32(1))) >> np.uint32(20)) - np.uint32(120 << 3)
+    sub = (c.view(np.float32) * np.float32(512.0) + np.float32(8388608.0)).view(np.uint32) & np.uint32(15)
+    return np.where(c < np.uint32(0x3C800000), sub, norm) | s
+
+
+def mxfp8_kernel_model(x, src: str = "float32") -> tuple:
+    """``kernels/mx_quantize.hip`` step by step, in uint32 and float32
+    operations only.  Per block: the maximum of the keys ``|x| bits + 2^23``
+    as signed integers (inf and NaN are negative there, so it is the maximum
+    over the finite values), the scale byte ``max(E − 8, 0)`` from that
+    maximum's exponent field E (127 when it is zero or nothing is finite).
+    Per element: the conversion of ``x · 2^-e`` (:func:`e4m3_convert_model`;
+    one float32 multiply by ``2^-e``, bits ``(254 − byte) << 23``, always a
+    normal number — the product is exact unless it underflows, where the code
+    is a signed zero like the instruction's, which scales and rounds once),
+    then the kernels' repair: an all-ones code becomes 0x7e under its sign
+    (saturation) unless the input was a NaN, which loses its sign.  ``x``:
+    float32 values, or bf16 bit patterns (uint16) with ``src="bfloat16"``;
+    blocks of 32 along the last axis.  Returns ``(codes uint8 like x, scales
+    uint8 [..., K/32])``."""
+    src = _src_name(src)
+    x = np.asarray(x)
+    if src == "bfloat16":
+        if x.dtype != np.uint16:
+            raise ValueError("bfloat16 input is given as uint16 bit patterns")
+        u = x.astype(np.uint32) << np.uint32(16)
+    else:
+        u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    if u.shape[-1] % MX_BLOCK:
+        raise ValueError(f"the last axis ({u.shape[-1]}) must be a multiple of the block ({MX_BLOCK})")
+    ub = np.ascontiguousarray(u).reshape(-1, MX_BLOCK)
+    key = ((ub & np.uint32(0x7FFFFFFF)) + np.uint32(0x00800000)).view(np.int32)
+    amax = (np.maximum(key.max(axis=1), np.int32(0x00800000)) - np.int32(0x00800000)).astype(np.uint32)
+    field = (amax >> np.uint32(23)).astype(np.int32)
+    sb = np.where(amax == 0, 127, np.maximum(field - 8, 0)).astype(np.uint32)
+    mult = ((np.uint32(254) - sb) << np.uint32(23)).view(np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        w = e4m3_convert_model(ub.view(np.float32) * mult[:, None])
+    nan = (np.uint32(0x80000000) - key.view(np.uint32)).view(np.int32) < 0
+    full = (w & np.uint32(0x7F)) == np.uint32(0x7F)
+    codes = np.where(nan, np.uint32(0x7F), np.where(full, w - np.uint32(1), w))
+    return codes.astype(np.uint8).reshape(x.shape), sb.astype(np.uint8).reshape(x.shape[:-1] + (-1,))
+
+
+_FLAGS = ("read", "partial_read", "write", "elements_per_work_item", "gather_resident")
+
+
+class MxFp8Quantizer:
+    """``[rows][K]`` fp32 or bf16 → MXFP8 through ``compute()``.
+
+    ``X`` (``rows·K`` of the source type; bf16 as the uint16-storage bf16
+    ClArray) is the input, ``codes`` (``"float8_e4m3fn"``), ``scales`` (uint8,
+    ``rows·K/32``, row-major) and ``packed`` (uint32, ``rows·K/128``, the
+    layout of :func:`~cekirdekler_amd.ops.gemm.pack_mx_scales`) the outputs;
+    ``packed`` exists when rows % 64 = 0 and K % 128 = 0 and is None
+    otherwise.  Arrays passed in are adopted (``x``: an input that already
+    lives in a ClArray, e.g. another kernel's output); their transfer flags
+    are as they were when :meth:`run` returns.
+
+    The number of blocks ``rows·K/32`` must be a multiple of 64."""
+
+    def __init__(self, rows: int, K: int, src: str = "float32", devices=None,
+                 cruncher: ClNumberCruncher | None = None, codes: ClArray | None = None,
+                 scales: ClArray | None = None, packed: ClArray | None = None, x: ClArray | None = None):
+        self.src = _src_name(src)
+        rows, K = int(rows), int(K)
+        if rows <= 0 or K <= 0 or K % MX_BLOCK:
+            raise ValueError(f"rows and K must be positive and K % {MX_BLOCK} = 0 (got {rows}, {K})")
+        self.rows, self.K = rows, K
+        self.blocks = rows * K // MX_BLOCK
+        if self.blocks % LOCAL:
+            raise ValueError(f"the number of blocks rows*K/{MX_BLOCK} ({self.blocks}) must be a multiple of {LOCAL}")
+        self.kernel = QUANTIZE_KERNELS[self.src]
+        self.has_packed = rows % 64 == 0 and K % 128 == 0
+        n = rows * K
+        want = [("x", x, n, np.float32 if self.src == "float32" else np.uint16),
+                ("codes", codes, n, np.uint8), ("scales", scales, self.blocks, np.uint8)]
+        if self.has_packed:
+            want.append(("packed", packed, n // 128, np.uint32))
+        elif packed is not None:
+            raise ValueError(f"packed scales need rows % 64 = 0 and K % 128 = 0 (got {rows}, {K})")
+        for name, arr, length, dt in want:
+            if arr is not None and (not isinstance(arr, ClArray) or arr.N != length or arr.array.dtype != dt):
+                raise ValueError(f"{name} must be a ClArray of {length} {np.dtype(dt).name} elements")
+        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("mx_quantize"))
+        have = {k.split(":")[0] for k in self.cr.kernel_names}
+        missing = [k for k in LIBRARY["mx_quantize"] if k not in have]
+        if missing:
+            raise ClComputeError(f"the cruncher has no kernel {missing[0]!r}: it was built without "
+                                 "library('mx_quantize')")
+        self.X = x if x is not None else ClArray(n, "float32" if self.src == "float32" else "bfloat16")
+        self.codes = codes if codes is not None else ClArray(n, "float8_e4m3fn")
+        self.scales = scales if scales is not None else ClArray(self.blocks, np.uint8)
+        self.packed = None
+        if self.has_packed:
+            self.packed = packed if packed is not None else ClArray(n // 128, np.uint32)
+        self.dims = ClArray(np.array([rows, K], np.int32))
+        self.records = []
+
+    def _arrays(self) -> list:
+        return [a for a in (self.X, self.codes, self.scales, self.packed, self.dims) if a is not None]
+
+    def run(self, compute_id: int = 7001, upload: bool = True, download: bool = True, pack: bool = True,
+            pack_compute_id: int | None = None) -> None:
+        """One ``compute()`` of the quantise kernel over the blocks, then, with
+        ``pack`` and a packed array, one of the pack kernel over the packed
+        dwords under ``pack_compute_id`` (default ``compute_id + 1``).
+        ``upload=False``: X is resident already (an earlier call, or another
+        kernel wrote it).  ``download=False``: the outputs stay in device
+        memory.  On several devices the outputs are gathered device to device:
+        every device holds all of them afterwards, and the pack compute reads
+        the scales as a resident whole.  ``records`` holds the computes'
+        ``last_record()`` afterwards (quantise, then pack)."""
+        saved = [(a, [getattr(a, f) for f in _FLAGS]) for a in self._arrays()]
+        gather = self.cr.number_of_devices > 1
+        try:
+            for a, epw, rd, wr, ga in ((self.X, MX_BLOCK, upload, False, False),
+                                       (self.codes, MX_BLOCK, False, download, gather),
+                                       (self.scales, 1, False, download, gather)):
+                a.partial_read = False
+                a.read, a.write, a.elements_per_work_item, a.gather_resident = rd, wr, epw, ga
+            self.X.next_param(self.codes, self.scales).compute(self.cr, compute_id, self.kernel, self.blocks, LOCAL)
+            self.records = [self.cr.last_record()]
+            if pack and self.packed is not None:
+                self.scales.write = self.scales.gather_resident = False
+                self.dims.partial_read = self.dims.write = self.dims.gather_resident = False
+                self.dims.read = True  # 8 bytes: every device has them whatever the split was before
+                p = self.packed
+                p.partial_read = p.read = False
+                p.write, p.elements_per_work_item, p.gather_resident = download, 1, gather
+                self.dims.next_param(self.scales, p).compute(
+                    self.cr, compute_id + 1 if pack_compute_id is None else pack_compute_id, PACK_KERNEL,
+                    p.N, LOCAL)
+                self.records.append(self.cr.last_record())
+        finally:
+            for a, flags in saved:
+                for f, v in zip(_FLAGS, flags):
+                    setattr(a, f, v)
