@@ -460,6 +460,14 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
         const int px = __hip_atomic_load(&tile_cnt[4 * t + 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (px != (int)my_xcc + 1) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (dims[7] == -1) {
+          // debug (dims[7] == -1): the owner claims at its start.  A helper
+          // with a short K-range can be here before that owner has started;
+          // it waits (bounded) for the claim, so that every owner falls back.
+          for (int spins = 0; spins < (1 << 20) && __hip_atomic_load(&tile_cnt[4 * t], __ATOMIC_RELAXED,
+                                                                     __HIP_MEMORY_SCOPE_AGENT) == 0; ++spins)
+            __builtin_amdgcn_s_sleep(2);
+        }
         int open = 0;
         int abort = 0;
         if (!__hip_atomic_compare_exchange_strong(&tile_cnt[4 * t], &open, 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,

@@ -374,8 +374,9 @@ class GemmBf16:
         self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library(*GEMM_LIBS))
         self.group_m = group_m
         # dims[7]: the owner's wait for the helper's partial, in polls (0: the
-        # kernel default, 65536; -1: the owner claims at once, -2 (halves
-        # tile): the helper claims the hand-back at once — forced fall-backs)
+        # kernel default, 65536; -1: the owner claims at once and the helper
+        # waits for that claim, so every owner falls back; -2 (halves tile):
+        # the helper claims the hand-back at once — forced fall-backs)
         self.dims = ClArray(np.array([M, N, K, group_m, self.split_k, shift, 0, int(handover_spin_limit)], np.int32))
         self.dims.write = False
         self.A = ClArray(M * K, "bfloat16")
