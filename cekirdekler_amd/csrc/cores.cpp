@@ -50,6 +50,11 @@ Cores::Cores(const std::vector<DeviceInfo>& devices, const std::string& source,
   pending_d2h_.resize(workers_.size());
   pending_span_end_.resize(workers_.size());
   order_events_.resize(workers_.size());
+  // one slot per worker from the start: the devices of a gathering call take
+  // their kernels-done events from their own threads at the same time, and a
+  // vector that grew on first use was resized by two of them at once
+  kdone_.assign(workers_.size(), nullptr);
+  pushed_.assign(workers_.size(), nullptr);
   if (const char* e = std::getenv("CEK_DEVICE_SPANS")) device_spans = std::string(e) != "0";
   if (const char* e = std::getenv("CEK_SINGLE_DEVICE_SPANS")) single_device_spans = std::string(e) == "1";
   if (const char* e = std::getenv("CEK_DEFER_DOWNLOADS")) deferred_downloads = std::string(e) != "0";
@@ -128,9 +133,10 @@ uint64_t Cores::d2d_copy(int ws, int wd, char* dst, const char* src, uint64_t by
   return bytes;
 }
 
+// v is kdone_ or pushed_: one slot per worker since the constructor, never
+// resized here (device threads call this at the same time, each for its own w)
 hipEvent_t Cores::gather_event(std::vector<hipEvent_t>& v, int w) {
-  if (v.size() < workers_.size()) v.resize(workers_.size(), nullptr);
-  if (!v[w]) {
+  if (!v.at(w)) {
     workers_[w]->set_device();
     CEK_HIP(hipEventCreateWithFlags(&v[w], hipEventDisableTiming));
   }
@@ -1265,6 +1271,15 @@ void Cores::flush_downloads(Worker& wk, hipStream_t next, const ComputeCall* c) 
 // 3-phase path never did and stays unlogged.  A stack value per call: no
 // allocation, the slice rules are inlined lambdas
 //   rule(array, begin, count) -> false: this array does not move here
+// Bytes of elements [begin, begin + count) that lie inside the array: what
+// Worker::h2d / d2h copy of a slice that runs past its end (a global offset
+// with an array sized for the global range alone)
+static uint64_t bytes_inside(const ArraySpec& a, uint64_t begin, uint64_t count) {
+  const uint64_t off = begin * a.elem_size;
+  if (off >= a.bytes) return 0;
+  return std::min<uint64_t>(count * a.elem_size, a.bytes - off);
+}
+
 struct Cores::Ordering {
   Cores& cs;
   Worker& wk;
@@ -1305,7 +1320,7 @@ struct Cores::Ordering {
       uint64_t b, n;
       if (a.zc || !a.partial || !rule(a, b, n)) continue;
       wk.h2d(l.s, a, b, n);
-      up += n * a.elem_size;
+      up += bytes_inside(a, b, n);
     }
     log("h2d", l, off, len);
   }
@@ -1319,7 +1334,7 @@ struct Cores::Ordering {
       uint64_t b, n;
       if (a.zc || !a.write || a.write_all || !rule(a, b, n)) continue;
       wk.d2h(l.s, a, b, n);
-      down += n * a.elem_size;
+      down += bytes_inside(a, b, n);
     }
     log("d2h", l, off, len);
   }
@@ -1435,7 +1450,7 @@ void Cores::run_3phase(Worker& wk, int gidx, const ComputeCall& c, long long ref
       pending_d2h_[w].push_back({s, a, b, n});
     else
       wk.d2h(s, a, b, n);
-    *d2h += n * a.elem_size;
+    *d2h += bytes_inside(a, b, n);
   }
   if (deferred_any && wk.gpu() && spans_on()) {
     // the span closes after the deferred download too
