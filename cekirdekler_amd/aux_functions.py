@@ -23,6 +23,8 @@ __device__ inline float cek_bf16_to_f32(unsigned short h) {
   union { unsigned int u; float f; } c; c.u = ((unsigned int)h) << 16; return c.f; }
 __device__ inline unsigned short cek_f32_to_bf16(float f) {   // round to nearest even
   union { unsigned int u; float f; } c; c.f = f;
+  // NaN: sign and top payload bits kept, quiet bit set (rounding would carry it into Inf or 0)
+  if ((c.u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((c.u >> 16) | 0x0040u);
   unsigned int r = 0x7fffu + ((c.u >> 16) & 1u);
   return (unsigned short)((c.u + r) >> 16); }
 """,

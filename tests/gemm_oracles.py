@@ -237,6 +237,7 @@ def range_ends(shape, seed=5, fmt="bf16", kind="large"):
 
 
 FINITE, POS_INF, NEG_INF, NAN = 0, 1, 2, 3
+SIGNALLING_NAN = np.uint32(0x7F800001)
 
 
 @functools.lru_cache(maxsize=None)
@@ -259,7 +260,10 @@ def nonfinite(shape, fmt="bf16"):
     assert (bi[:, k1] > 0).any() and (bi[:, k1] < 0).any()
     a = ai.astype(np.float32)
     a[m1, k1] = np.inf
-    a[m2, k2] = np.nan
+    # a signalling NaN with the lowest payload bit only (0x7F800001): an
+    # encoder that adds its rounding increment to it returns +Inf
+    a.view(np.uint32)[m2, k2] = SIGNALLING_NAN
+    assert np.isnan(a[m2, k2])
     ai[m1, k1] = ai[m2, k2] = 0
     expected = _int_product(ai, bi)
     cls = np.full((M, N), FINITE, np.int8)
@@ -387,7 +391,8 @@ def _dot(a, b):
 
 
 def _ops64(a, b):
-    return np.asarray(a, np.float64), np.asarray(b, np.float64)
+    with np.errstate(invalid="ignore"):  # widening the signalling NaN of `nonfinite` raises the flag
+        return np.asarray(a, np.float64), np.asarray(b, np.float64)
 
 
 def emu_chain_f32(a, b):

@@ -150,3 +150,98 @@ def test_verify_shells_full_checks_every_block(cpu_cr):
     assert blocks == 16 and err < 1e-6
     g.C.array[5] += 1.0
     assert g.verify_shells_full(P, device="cpu")[0] > 1e-4
+
+
+# --------------------------------------------------------------------------- the bf16 codec
+
+BF16_AUX_SRC = """
+__global__ void enc(const float* f, unsigned short* h) {
+  long long i = get_global_id(0);
+  h[i] = cek_f32_to_bf16(f[i]);
+}
+__global__ void dec(const unsigned short* h, float* f) {
+  long long i = get_global_id(0);
+  f[i] = cek_bf16_to_f32(h[i]);
+}
+"""
+# NaNs whose rounding increment carries: into +Inf, -0, +0 and -Inf
+BF16_NAN_PATTERNS = np.array([0x7F800001, 0x7FFFFFFF, 0xFFFFFFFF, 0xFF800001], np.uint32)
+
+
+def bf16_codec_inputs():
+    """fp32 bit patterns: the four NaNs an adding encoder loses, further NaNs
+    of both signs, ±Inf, the largest finite values (they round to Inf), every
+    tie of one binade with its neighbours, subnormals, zeros and 200 000
+    random patterns; padded to a multiple of 64."""
+    rng = np.random.default_rng(7)
+    ties = (0x3F800000 + (np.arange(128, dtype=np.uint32) << 16) + 0x8000)  # both parities of the kept bit
+    u = np.concatenate([
+        BF16_NAN_PATTERNS, np.array([0x7FC00000, 0xFFC00000, 0x7F800100, 0xFF80FFFF, 0x7FBFFFFF], np.uint32),
+        np.array([0x7F800000, 0xFF800000, 0x7F7FFFFF, 0xFF7FFFFF, 0x7F7F8000, 0x7F7F7FFF], np.uint32),
+        ties, ties - 1, ties + 1, ties | 0x80000000,
+        np.array([0, 0x80000000, 1, 0x80000001, 0x7FFF, 0x8000, 0x8001, 0x18000, 0x007FFFFF, 0x807F8000], np.uint32),
+        rng.integers(0, 2 ** 32, 200_000, dtype=np.uint64).astype(np.uint32)])
+    return np.concatenate([u, np.zeros(-len(u) % 64, np.uint32)])
+
+
+def assert_bf16_like_torch(x_bits, got):
+    """Bit for bit torch's fp32 → bf16 conversion, except at NaNs: there the
+    result must be a NaN of the input's sign (torch returns one canonical
+    NaN for every NaN input, so its sign is not the reference)."""
+    import torch
+
+    want = torch.from_numpy(x_bits.view(np.float32).copy()).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    nan = (x_bits & 0x7FFFFFFF) > 0x7F800000
+    assert nan.sum() > 500 and (~nan).sum() > 190_000  # one random pattern in 256 is a NaN
+    assert got.dtype == np.uint16
+    bad = np.flatnonzero(got[~nan] != want[~nan])
+    assert bad.size == 0, (bad.size, [hex(v) for v in x_bits[~nan][bad[:4]]], got[~nan][bad[:4]], want[~nan][bad[:4]])
+    g, w = got[nan].astype(np.uint32), want[nan].astype(np.uint32)
+    assert ((w & 0x7FFF) > 0x7F80).all()                      # torch: NaN
+    assert ((g & 0x7FFF) > 0x7F80).all(), [hex(v) for v in x_bits[nan][(g & 0x7FFF) <= 0x7F80][:4]]
+    assert np.array_equal(g >> 15, x_bits[nan] >> 31)         # the sign is kept
+    assert np.array_equal(g, (x_bits[nan] >> 16) | 0x40)      # and the top payload bits, quiet bit set
+
+
+def bf16_aux_codec_case(devices):
+    """cek_f32_to_bf16 and cek_bf16_to_f32 on ``devices`` over
+    bf16_codec_inputs, one launch each: the encoder as assert_bf16_like_torch
+    has it, the decoder the exact widening.  (Shared with the GPU tier.)"""
+    from cekirdekler_amd.ops.gemm import from_bf16_bits, to_bf16_bits
+
+    cr = ck.ClNumberCruncher(devices, ck.ClBuiltInAuxilliaryFunctions(bf16=True).wrap(BF16_AUX_SRC))
+    assert cr.error_code() == 0, cr.error_message()
+    u = bf16_codec_inputs()
+    src = ck.ClArray(u.view(np.float32).copy())
+    enc = ck.ClArray(np.zeros(len(u), np.uint16))
+    src.write = False
+    src.next_param(enc).compute(cr, 1, "enc", len(u), 64)
+    assert_bf16_like_torch(u, enc.array)
+    np.testing.assert_array_equal(enc.array, to_bf16_bits(u.view(np.float32)))
+    back = ck.ClArray(np.zeros(len(u), np.float32))
+    enc.write = False
+    enc.next_param(back).compute(cr, 2, "dec", len(u), 64)
+    np.testing.assert_array_equal(back.array.view(np.uint32), enc.array.astype(np.uint32) << 16)
+    np.testing.assert_array_equal(back.array.view(np.uint32), from_bf16_bits(enc.array).view(np.uint32))
+    cr.dispose()
+
+
+def test_bf16_encoder_keeps_every_nan():
+    from cekirdekler_amd.ops.gemm import from_bf16_bits, to_bf16_bits
+
+    got = to_bf16_bits(BF16_NAN_PATTERNS.view(np.float32))
+    np.testing.assert_array_equal(got, [0x7FC0, 0x7FFF, 0xFFFF, 0xFFC0])
+    assert np.isnan(from_bf16_bits(got)).all()
+    np.testing.assert_array_equal(to_bf16_bits(np.array([np.inf, -np.inf, 3.4028235e38, -3.4028235e38], np.float32)),
+                                  [0x7F80, 0xFF80, 0x7F80, 0xFF80])
+
+
+def test_bf16_encoder_matches_torch_bit_for_bit():
+    from cekirdekler_amd.ops.gemm import to_bf16_bits
+
+    u = bf16_codec_inputs()
+    assert_bf16_like_torch(u, to_bf16_bits(u.view(np.float32)))
+
+
+def test_aux_bf16_codec_on_cpu_device():
+    bf16_aux_codec_case(ck.ClPlatforms.all().cpus(True))

@@ -240,3 +240,12 @@ def test_resident_verify_reports_zero_on_exact_data(crunchers, fmt, tile):
         err, checked = g.verify_full(g.cid)
         assert checked == g.tiles and err == 0.0, (err, checked)
         assert g.verify(g.cid) == 0.0
+
+
+def test_aux_bf16_codec_on_gpu():
+    """cek_f32_to_bf16 / cek_bf16_to_f32 on the GPU over the inputs of the
+    CPU tier (NaNs of every kind, ±Inf, the largest finite values, every tie
+    of a binade, subnormals, 200 000 random patterns), one launch each way."""
+    from test_gemm_host import bf16_aux_codec_case
+
+    bf16_aux_codec_case(ck.ClPlatforms.all().gpus()[0])
