@@ -8,7 +8,7 @@ split on every call with the same compute id.
 """
 from ._native import CekError, cek, gpu_available
 from .arrays import (BFLOAT16, ClArray, ClBf16Array, ClByteArray, ClCharArray, ClDoubleArray,
-                     ClFloatArray, ClFp8Array, ClIntArray, ClLongArray, ClParameterGroup, ClUIntArray, FastArr)
+                     ClFloatArray, ClFp4x2Array, ClFp8Array, ClIntArray, ClLongArray, ClParameterGroup, ClUIntArray, FastArr)
 from .cruncher import (PIPELINE_DRIVER, PIPELINE_EVENT, AcceleratorType, ClComputeError,
                        ClNumberCruncher, ClUserEvent, Cores)
 from .aux_functions import ClBuiltInAuxilliaryFunctions
@@ -19,7 +19,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "AcceleratorType", "BFLOAT16", "ClBuiltInAuxilliaryFunctions", "CekError", "ClArray", "ClBf16Array", "ClByteArray", "ClCharArray",
-    "ClComputeError", "ClDevice", "ClDevices", "ClDoubleArray", "ClFloatArray", "ClFp8Array", "ClIntArray",
+    "ClComputeError", "ClDevice", "ClDevices", "ClDoubleArray", "ClFloatArray", "ClFp4x2Array", "ClFp8Array", "ClIntArray",
     "ClLongArray", "ClNumberCruncher", "ClParameterGroup", "ClPlatform", "ClPlatforms", "ClUIntArray", "ClUserEvent",
     "Cores", "FastArr", "PIPELINE_DRIVER", "PIPELINE_EVENT", "cek", "gpu_available", "license_text",
 ]

@@ -37,6 +37,11 @@ BFLOAT16 = "bfloat16"
 # the ``is_fp8`` flag, as bf16 is uint16 storage plus ``is_bf16``
 FLOAT8_E4M3FN = "float8_e4m3fn"
 _FP8_NAMES = ("float8_e4m3fn", "fp8", "e4m3")
+# OCP e2m1 (MXFP4's element), two per byte: uint8 storage plus the ``is_fp4``
+# flag; element 2i in bits 0-3 of byte i, element 2i + 1 in bits 4-7.  The
+# length of such an array counts bytes, that is pairs.
+FLOAT4_E2M1FN_X2 = "float4_e2m1fn_x2"
+_FP4_NAMES = ("float4_e2m1fn_x2", "fp4x2", "e2m1x2")
 
 _DTYPES = {
     "float32": np.float32, "float": np.float32, "f32": np.float32,
@@ -57,7 +62,7 @@ def _resolve_dtype(dtype) -> tuple[np.dtype, bool]:
         key = dtype.lower()
         if key in ("bfloat16", "bf16"):
             return np.dtype(np.uint16), True
-        if key in _FP8_NAMES:
+        if key in _FP8_NAMES or key in _FP4_NAMES:
             return np.dtype(np.uint8), False
         if key in _DTYPES:
             return np.dtype(_DTYPES[key]), False
@@ -67,7 +72,7 @@ def _resolve_dtype(dtype) -> tuple[np.dtype, bool]:
         if isinstance(dtype, torch.dtype):
             if dtype == torch.bfloat16:
                 return np.dtype(np.uint16), True
-            if dtype == torch.float8_e4m3fn:
+            if dtype == torch.float8_e4m3fn or dtype == _torch_fp4x2():
                 return np.dtype(np.uint8), False
             return np.dtype(torch.empty(0, dtype=dtype).numpy().dtype), False
     except Exception:  # pragma: no cover
@@ -85,6 +90,24 @@ def _is_fp8(dtype) -> bool:
         return isinstance(dtype, torch.dtype) and dtype == torch.float8_e4m3fn
     except ImportError:  # pragma: no cover
         return False
+
+
+def _torch_fp4x2():
+    """``torch.float4_e2m1fn_x2`` where the installed torch has it, else None."""
+    try:
+        import torch
+
+        return getattr(torch, "float4_e2m1fn_x2", None)
+    except ImportError:  # pragma: no cover
+        return None
+
+
+def _is_fp4(dtype) -> bool:
+    """``dtype`` names packed e2m1 pairs (storage: :func:`_resolve_dtype` gives uint8)."""
+    if isinstance(dtype, str):
+        return dtype.lower() in _FP4_NAMES
+    t = _torch_fp4x2()
+    return t is not None and dtype is t
 
 
 _uid_counter = itertools.count(1)
@@ -124,6 +147,7 @@ class FastArr:
     def __init__(self, n: int, dtype=np.float32, alignment: int = 4096):
         np_dtype, self.is_bf16 = _resolve_dtype(dtype)
         self.is_fp8 = _is_fp8(dtype)
+        self.is_fp4 = _is_fp4(dtype)
         if n <= 0:
             raise ValueError("FastArr length must be positive")
         self._n = int(n)
@@ -226,6 +250,7 @@ ClByteArray = _typed_fastarr("ClByteArray", np.uint8)
 ClCharArray = _typed_fastarr("ClCharArray", np.uint16)
 ClBf16Array = _typed_fastarr("ClBf16Array", BFLOAT16)
 ClFp8Array = _typed_fastarr("ClFp8Array", FLOAT8_E4M3FN)
+ClFp4x2Array = _typed_fastarr("ClFp4x2Array", FLOAT4_E2M1FN_X2)
 
 
 # --------------------------------------------------------------------------- ClArray
@@ -257,6 +282,7 @@ class ClArray:
         self._torch_ref = None
         self.is_bf16 = False
         self.is_fp8 = False
+        self.is_fp4 = False
         if data is None:
             self._np = None
         elif isinstance(data, (int, np.integer)):
@@ -264,15 +290,17 @@ class ClArray:
             if fast is False:
                 np_dtype, self.is_bf16 = _resolve_dtype(dtype)
                 self.is_fp8 = _is_fp8(dtype)
+                self.is_fp4 = _is_fp4(dtype)
                 self._np = np.zeros(n, np_dtype)
             else:
                 self._fast = FastArr(n, dtype or np.float32, alignment)
-                self.is_bf16, self.is_fp8 = self._fast.is_bf16, self._fast.is_fp8
+                self.is_bf16, self.is_fp8, self.is_fp4 = self._fast.is_bf16, self._fast.is_fp8, self._fast.is_fp4
         elif isinstance(data, FastArr):
             self._fast = data
-            self.is_bf16, self.is_fp8 = data.is_bf16, data.is_fp8
+            self.is_bf16, self.is_fp8, self.is_fp4 = data.is_bf16, data.is_fp8, data.is_fp4
         elif isinstance(data, ClArray):
             self._fast, self._np, self.is_bf16, self.is_fp8 = data._fast, data._np, data.is_bf16, data.is_fp8
+            self.is_fp4 = data.is_fp4
         else:
             self._wrap_host(data, dtype)
         # reference defaults (ClArray.cs:838-845)
@@ -320,6 +348,9 @@ class ClArray:
                 elif t.dtype == torch.float8_e4m3fn:
                     self.is_fp8 = True
                     self._np = t.view(torch.uint8).numpy()
+                elif _torch_fp4x2() is not None and t.dtype == _torch_fp4x2():
+                    self.is_fp4 = True
+                    self._np = t.view(torch.uint8).numpy()
                 else:
                     self._np = t.numpy()
                 return
@@ -329,6 +360,7 @@ class ClArray:
         if dtype is not None:
             np_dtype, self.is_bf16 = _resolve_dtype(dtype)
             self.is_fp8 = _is_fp8(dtype)
+            self.is_fp4 = _is_fp4(dtype)
             if arr.dtype != np_dtype:
                 arr = arr.astype(np_dtype)
         if not arr.flags.c_contiguous:
@@ -393,6 +425,8 @@ class ClArray:
 
     def _storage_dtype(self, np_dtype):
         """What to allocate a FastArr of this array's element type with."""
+        if self.is_fp4:
+            return FLOAT4_E2M1FN_X2
         return BFLOAT16 if self.is_bf16 else FLOAT8_E4M3FN if self.is_fp8 else np_dtype
 
     @property
@@ -401,8 +435,9 @@ class ClArray:
 
     @property
     def dtype_name(self) -> str:
-        """The element type's name: ``"bfloat16"`` / ``"float8_e4m3fn"`` for
-        the flagged bit-pattern arrays, numpy's name otherwise."""
+        """The element type's name: ``"bfloat16"`` / ``"float8_e4m3fn"`` /
+        ``"float4_e2m1fn_x2"`` for the flagged bit-pattern arrays, numpy's
+        name otherwise."""
         return str(self.dtype)
 
     @property
@@ -468,7 +503,8 @@ class ClArray:
 
     def as_torch(self):
         """Zero-copy torch CPU tensor view (bf16 arrays come back as bfloat16,
-        fp8 arrays as float8_e4m3fn)."""
+        fp8 arrays as float8_e4m3fn, fp4x2 arrays as float4_e2m1fn_x2 where
+        the installed torch has that type and as uint8 otherwise)."""
         import torch
 
         t = torch.from_numpy(self.array)
@@ -476,6 +512,8 @@ class ClArray:
             t = t.view(torch.bfloat16)
         elif self.is_fp8:
             t = t.view(torch.float8_e4m3fn)
+        elif self.is_fp4 and _torch_fp4x2() is not None:
+            t = t.view(_torch_fp4x2())
         return t
 
     to_torch = as_torch

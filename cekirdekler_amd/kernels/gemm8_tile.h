@@ -1,8 +1,10 @@
-// The tile function of the one-byte-per-element GEMMs: sgemm_fp8.hip (plain
-// e4m3fn) and sgemm_mxfp8.hip (e4m3fn with E8M0 block scales, MX = true).
+// The tile function of the GEMMs whose operands are staged as bytes:
+// sgemm_fp8.hip (plain e4m3fn), sgemm_mxfp8.hip (e4m3fn with E8M0 block
+// scales, MX = true) and sgemm_mxfp4.hip (e2m1, two per byte, F4 = true).
 // Byte geometry, staging and the ping-pong structure are written once here;
-// the two files differ in the scale operands of the 16x16x128 instruction
-// (and the loads that feed them) and in nothing else.  sgemm_fp8.hip's device code is
+// the two fp8 files differ in the scale operands of the 16x16x128 instruction
+// (and the loads that feed them) and in nothing else, and the 4-bit one in
+// what F4 says below.  sgemm_fp8.hip's device code is
 // byte-identical to what it was when this function lived in that file
 // (tools/kernel_identity.py).
 #pragma once
@@ -42,13 +44,18 @@ __device__ __forceinline__ void cek_static_for(F&& f) {
 // X128: the scaled 16x16x128 instruction instead of four 16x16x32 steps.
 // MX: block scales (sgemm_mxfp8.hip has the map, the packed scale layout and
 // the vmcnt argument); SAp / SBp are the packed scales, unused otherwise.
-template <int WM, int WN, int FM, int FN, int MODE, bool X128, bool MX = false>
+// F4: e2m1 operands, two per byte (sgemm_mxfp4.hip).  The row pitch is K/2
+// bytes and a K-tile of 128 B holds 256 k: two scaled instructions per
+// fragment pair, step s on the 16 B of read s with the scales of 128-k step
+// 2·kt + s.  Everything written in bytes stays as it is.
+template <int WM, int WN, int FM, int FN, int MODE, bool X128, bool MX = false, bool F4 = false>
 __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const uint8_t* __restrict__ A,
                                            const uint8_t* __restrict__ Bt, float* __restrict__ C, char* smem,
                                            long long off, const int* __restrict__ SAp = nullptr,
                                            const int* __restrict__ SBp = nullptr) {
   static_assert(MODE == 0 || MODE == 4, "MODE is 0 or 4");
   static_assert(!MX || (X128 && FM % 4 == 0 && FN % 4 == 0), "MX: scaled instruction, 64-row scale groups");
+  static_assert(!F4 || MX, "F4: block-scaled only");
   constexpr int BM = WM * 16 * FM, BN = WN * 16 * FN, BK = 128;
   constexpr int NWAVES = WM * WN, NT = 64 * NWAVES;
   constexpr int A_BYTES = BM * BK, B_BYTES = BN * BK, STAGE = A_BYTES + B_BYTES;
@@ -65,26 +72,27 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
   int tm, tn;
   if (!cek_tile_lookup(dims, GM, t, ntm, ntn, tm, tn)) return;
   const int m0 = tm * BM, n0 = tn * BN;
-  const int nk = K / BK, ks = 0;
+  const int KB = F4 ? K / 2 : K;  // row pitch in bytes
+  const int nk = KB / BK, ks = 0;
 
   // ---- staging (geometry: gemm_parts.h) ----
-  const unsigned lane_off = cek_stage_lane_off<1>(lane, K);
+  const unsigned lane_off = cek_stage_lane_off<1>(lane, KB);
   const int sw = MODE == 4 ? wave % (NWAVES / 2) : wave;  // staging wave index
-  const char* a_wave = (const char*)(A + (size_t)(m0 + sw * A_INSTR * 8) * K);
-  const char* b_wave = (const char*)(Bt + (size_t)(n0 + sw * B_INSTR * 8) * K);
+  const char* a_wave = (const char*)(A + (size_t)(m0 + sw * A_INSTR * 8) * KB);
+  const char* b_wave = (const char*)(Bt + (size_t)(n0 + sw * B_INSTR * 8) * KB);
   // MODE 0: K-tile kt into whole stage `buf` (A rows, then Bt rows)
   auto stage = [&](int buf, int kt) {
-    cek_stage_rows<A_INSTR, 1>(a_wave, lane_off, K, ks, kt, smem + buf * STAGE, sw);
-    cek_stage_rows<B_INSTR, 1>(b_wave, lane_off, K, ks, kt, smem + buf * STAGE + A_BYTES, sw);
+    cek_stage_rows<A_INSTR, 1>(a_wave, lane_off, KB, ks, kt, smem + buf * STAGE, sw);
+    cek_stage_rows<B_INSTR, 1>(b_wave, lane_off, KB, ks, kt, smem + buf * STAGE + A_BYTES, sw);
   };
   // MODE 4: two A buffers followed by three Bt buffers
   char* const a_base = smem;
   char* const b_base = smem + 2 * A_BYTES;
   auto stage_a4 = [&](int kt) {
-    cek_stage_rows<A_INSTR, 1>(a_wave, lane_off, K, ks, kt, a_base + (kt & 1) * A_BYTES, sw);
+    cek_stage_rows<A_INSTR, 1>(a_wave, lane_off, KB, ks, kt, a_base + (kt & 1) * A_BYTES, sw);
   };
   auto stage_b4 = [&](int kt) {
-    cek_stage_rows<B_INSTR, 1>(b_wave, lane_off, K, ks, kt, b_base + (kt % 3) * B_BYTES, sw);
+    cek_stage_rows<B_INSTR, 1>(b_wave, lane_off, KB, ks, kt, b_base + (kt % 3) * B_BYTES, sw);
   };
 
   // Fragment read offsets (bytes) inside a stage: row (wr·16FM + i·16 + l%16),
@@ -109,7 +117,9 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
   // holds fragments 4d .. 4d+3 (byte i & 3) for this lane's (row fr, MX block
   // fq); `sa` / `sb` are those of the K-tile being multiplied, `sa_n` / `sb_n`
   // the prefetch of the next one.
-  constexpr int SA_N = MX ? FM / 4 : 1, SB_N = MX ? FN / 4 : 1;
+  // F4: the dwords of step 0, then those of step 1 (index s · F/4 + d).
+  constexpr int SA_G = MX ? FM / 4 : 1, SB_G = MX ? FN / 4 : 1, STEPS = F4 ? 2 : 1;
+  constexpr int SA_N = SA_G * STEPS, SB_N = SB_G * STEPS;
   int sa[SA_N], sb[SB_N], sa_n[SA_N], sb_n[SB_N];
   // The loads are inline assembly on purpose.  A load the compiler knows of
   // makes it guard the scale registers with a wait of its own, and among the
@@ -124,19 +134,26 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
   // number of loads and none is out of bounds — and step one K-tile (M and N
   // dwords) per call while there is one, instead of being recomputed: the
   // 64-bit multiplies would sit ahead of the staging issue in every iteration.
+  // F4: a K-tile is two 128-k steps, M (N) dwords apart; the pointers step both.
   const int lane4 = lane * 4;
   const int* pa = SAp + (MX ? (m0 + wr * 16 * FM) / 64 * 64 : 0);
   const int* pb = SBp + (MX ? (n0 + wc * 16 * FN) / 64 * 64 : 0);
   auto ld_scales = [&](int kt) {
 #pragma unroll
     for (int d = 0; d < SA_N; ++d)
-      asm volatile("global_load_dword %0, %1, %2" : "=v"(sa_n[d]) : "v"(lane4), "s"(pa + d * 64) : "memory");
+      asm volatile("global_load_dword %0, %1, %2"
+                   : "=v"(sa_n[d])
+                   : "v"(lane4), "s"(pa + (d / SA_G) * M + (d % SA_G) * 64)
+                   : "memory");
 #pragma unroll
     for (int d = 0; d < SB_N; ++d)
-      asm volatile("global_load_dword %0, %1, %2" : "=v"(sb_n[d]) : "v"(lane4), "s"(pb + d * 64) : "memory");
+      asm volatile("global_load_dword %0, %1, %2"
+                   : "=v"(sb_n[d])
+                   : "v"(lane4), "s"(pb + (d / SB_G) * N + (d % SB_G) * 64)
+                   : "memory");
     const bool more = kt + 1 < nk;
-    pa += more ? M : 0;
-    pb += more ? N : 0;
+    pa += more ? STEPS * M : 0;
+    pb += more ? STEPS * N : 0;
   };
   // after a vmcnt wait that covers the prefetch: the prefetch becomes current
   auto next_scales = [&] {
@@ -197,9 +214,28 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
       });
     });
   };
+  // F4: two steps of 128 k, each the 16 B of one read (formats 4 = e2m1: the
+  // instruction takes the low four registers of the operand and ignores the
+  // rest), step 0 over every fragment pair before step 1, so that the two
+  // instructions on one accumulator are FM·FN issues apart
+  auto mma128f4 = [&] {
+    cek_static_for<0, 2>([&](auto sc) {
+      cek_static_for<0, FM>([&](auto ic) {
+        cek_static_for<0, FN>([&](auto jc) {
+          constexpr int s = decltype(sc)::value, i = decltype(ic)::value, j = decltype(jc)::value;
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+              __builtin_shufflevector(fa[s][i], fa[s][i], 0, 1, 2, 3, -1, -1, -1, -1),
+              __builtin_shufflevector(fb[s][j], fb[s][j], 0, 1, 2, 3, -1, -1, -1, -1), acc[i][j], 4, 4, i & 3,
+              sa[s * SA_G + i / 4], j & 3, sb[s * SB_G + j / 4]);
+        });
+      });
+    });
+  };
   auto mmaall = [&] {
     __builtin_amdgcn_s_setprio(1);
-    if constexpr (MX) {
+    if constexpr (F4) {
+      mma128f4();
+    } else if constexpr (MX) {
       mma128mx();
     } else if constexpr (X128) {
       mma128();

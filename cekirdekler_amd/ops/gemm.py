@@ -1,6 +1,7 @@
 """Range-partitioned GEMMs: bf16 (the "SGEMM 8192² bf16" config of
-BASELINE.json), fp32 on the fp32 matrix cores, fp8 (OCP e4m3fn) and MXFP8
-(e4m3fn with one E8M0 scale per block of 32).
+BASELINE.json), fp32 on the fp32 matrix cores, fp8 (OCP e4m3fn), MXFP8
+(e4m3fn with one E8M0 scale per block of 32) and MXFP4 (e2m1, two per byte,
+with the same scales).
 
 ``C = A · Bᵀ`` with A ``[M][K]`` and Bt ``[N][K]`` bf16 row-major, C fp32 in
 tile-major layout (see ``kernels/sgemm_bf16.hip``).  The global range is one
@@ -158,6 +159,19 @@ MXFP8_TILES = {
 MXFP8_TILE_WAVES = {"256x256pbx": (2, 4, 8, 4), "128x128": (2, 2, 4, 4)}
 MX_BLOCK = 32  # elements per scale along K
 
+# MXFP4 tiles (kernels/sgemm_mxfp4.hip): the MXFP8 structures with e2m1
+# operands, two per byte, a K-tile of 128 B = 256 k as two scaled
+# instructions.  Throughput beside the MXFP8 256x256pbx of the same run:
+# profiles/gemm_mxfp4.md.
+MXFP4_TILES = {
+    # balanced-DMA ping-pong, packed scales global → VGPR one K-tile ahead:
+    # the GemmMxFp4 default
+    "256x256pbx": (256, 256, 512, "cek_sgemm_mxfp4_256x256pbx"),
+    # one LDS stage in flight, 4 waves: the simple kernel the other is judged against
+    "128x128": (128, 128, 256, "cek_sgemm_mxfp4_128x128"),
+}
+MXFP4_TILE_WAVES = {"256x256pbx": (2, 4, 8, 4), "128x128": (2, 2, 4, 4)}
+
 # tiles whose kernel stores C row-major ([M][N]) instead of tile-major
 ROW_MAJOR_TILES = {"256x256pbr"}
 # tiles with a split-K kernel variant ("<kernel>_sk", arrays + W + counters)
@@ -282,11 +296,113 @@ def unpack_mx_scales(p: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(x.transpose(1, 4, 3, 0, 2)).reshape(G * 64, KT * 4)  # g i fr kt fq
 
 
+# OCP e2m1 (MXFP4's element): code s e e m
+_FP4_E2M1 = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0,
+                      -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], np.float32)
+# the midpoints between neighbouring magnitudes; a value on midpoint i lies
+# between codes i and i + 1 and goes to the even one
+_FP4_MIDPOINTS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)
+FP4_E2M1_EMAX = 2  # exponent of e2m1's largest binade (4, 6)
+
+
+def to_fp4_e2m1_codes(x: np.ndarray) -> np.ndarray:
+    """fp32 (or fp64) → OCP e2m1 codes 0..15, one per element, as uint8: bit
+    layout ``s e e m``, codes 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6 and 8..15 their
+    negatives (−0 kept).  Round to nearest even (a value halfway between two
+    neighbours goes to the one whose mantissa bit is 0); finite values beyond
+    ±6 and ±inf SATURATE to ±6.  e2m1 has no NaN: a NaN gives code 0."""
+    x = np.asarray(x)
+    x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+    a = np.abs(x)
+    code = np.zeros(x.shape, np.uint8)
+    with np.errstate(invalid="ignore"):
+        for i, mid in enumerate(_FP4_MIDPOINTS):
+            code += (a >= mid) if i % 2 else (a > mid)
+    nan = np.isnan(x)
+    return np.where(nan, np.uint8(0), code | (np.signbit(x).astype(np.uint8) << 3)).astype(np.uint8)
+
+
+def from_fp4_e2m1_codes(c: np.ndarray) -> np.ndarray:
+    """OCP e2m1 codes (uint8, 0..15, one per element) → fp32, by table."""
+    c = np.asarray(c, dtype=np.uint8)
+    if c.size and int(c.max()) > 15:
+        raise ValueError("e2m1 codes are 0..15")
+    return _FP4_E2M1[c]
+
+
+def pack_fp4(codes: np.ndarray) -> np.ndarray:
+    """e2m1 codes ``[..., K]`` (0..15) → packed bytes ``[..., K/2]``: element
+    ``2i`` in bits 0–3 of byte ``i``, element ``2i + 1`` in bits 4–7 (the
+    public layout of every fp4x2 array)."""
+    c = np.asarray(codes, dtype=np.uint8)
+    if c.shape[-1] % 2:
+        raise ValueError(f"the last axis ({c.shape[-1]}) must be even")
+    if c.size and int(c.max()) > 15:
+        raise ValueError("e2m1 codes are 0..15")
+    return (c[..., 0::2] | (c[..., 1::2] << 4)).astype(np.uint8)
+
+
+def unpack_fp4(packed: np.ndarray) -> np.ndarray:
+    """Inverse of :func:`pack_fp4`: bytes ``[..., K/2]`` → codes ``[..., K]``."""
+    p = np.asarray(packed, dtype=np.uint8)
+    return np.stack((p & 15, p >> 4), axis=-1).reshape(p.shape[:-1] + (2 * p.shape[-1],))
+
+
+def to_mxfp4(x: np.ndarray, block: int = MX_BLOCK):
+    """OCP Microscaling (MX v1.0) MXFP4 along the last axis: ``(packed uint8
+    [..., K/2], scales uint8 [..., K/block])``, the elements packed as
+    :func:`pack_fp4` does.  Per block the shared exponent is ``e = floor(log2(max
+    |x| over the block's finite values)) − 2`` (2: the exponent of e2m1's
+    largest binade), clamped to [−127, 127], the scale byte ``e + 127`` and the
+    elements ``to_fp4_e2m1_codes(x · 2^−e)``: round to nearest even,
+    saturating, so scaled values in (6, 8) become ±6.  A block without a
+    finite nonzero value gets byte 127; ±inf → ±6 without a say in the scale.
+
+    NaN: e2m1 has no NaN code, so a NaN cannot stay in its element.  A block
+    that contains a NaN gets the scale byte ``0xFF`` (E8M0 NaN), which makes
+    the WHOLE block NaN in OCP MX (:func:`from_mxfp4`, the kernels); its NaN
+    elements get code 0 and its other elements the codes they would have had.
+    (:func:`to_mxfp8` never produces ``0xFF``: e4m3 has a NaN of its own.)
+
+    The scaling and the element rounding are done in float64, where both are
+    exact for float32 and float64 input alike."""
+    x = np.asarray(x)
+    x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+    K = x.shape[-1]
+    if block <= 0 or block % 2 or K % block:
+        raise ValueError(f"the last axis ({K}) must be a multiple of the block ({block}), the block even")
+    xb = x.reshape(x.shape[:-1] + (K // block, block)).astype(np.float64)
+    amax = np.where(np.isfinite(xb), np.abs(xb), 0.0).max(axis=-1)
+    _, ex = np.frexp(amax)  # amax = m · 2^ex, 0.5 <= m < 1: floor(log2 amax) = ex − 1
+    e = np.clip(np.where(amax > 0, ex.astype(np.int64) - 1 - FP4_E2M1_EMAX, 0), -127, 127)
+    with np.errstate(over="ignore", invalid="ignore"):
+        codes = to_fp4_e2m1_codes(np.ldexp(xb, -e[..., None]))
+    scales = np.where(np.isnan(xb).any(axis=-1), 0xFF, e + 127).astype(np.uint8)
+    return pack_fp4(codes.reshape(x.shape)), scales
+
+
+def from_mxfp4(packed: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """MXFP4 → float32: ``e2m1(code) · 2^(scale − 127)`` with one scale per
+    ``K / scales.shape[-1]`` elements of the last axis, K twice the packed
+    length; a scale byte ``0xFF`` makes its whole block NaN.  (The product is
+    taken in float64; what float32 cannot hold rounds, overflows or underflows.)"""
+    packed, scales = np.asarray(packed, np.uint8), np.asarray(scales, np.uint8)
+    nb = scales.shape[-1]
+    v = from_fp4_e2m1_codes(unpack_fp4(packed)).astype(np.float64)
+    shape = v.shape
+    v = v.reshape(scales.shape + (shape[-1] // nb,))
+    with np.errstate(over="ignore", invalid="ignore"):
+        return (v * e8m0_to_f64(scales)[..., None]).astype(np.float32).reshape(shape)
+
+
 def decode_operand(arr: ClArray) -> np.ndarray:
-    """The host array of a GEMM operand as numbers: bf16 and fp8 arrays hold
-    bit patterns (``is_fp8``; ``is_bf16`` or plain uint16 storage), every
-    other array its values."""
+    """The host array of a GEMM operand as numbers: bf16, fp8 and fp4x2 arrays
+    hold bit patterns (``is_fp8``; ``is_fp4``: two e2m1 codes per byte, so the
+    result is twice as long as the array; ``is_bf16`` or plain uint16
+    storage), every other array its values."""
     x = arr.array
+    if getattr(arr, "is_fp4", False):
+        return from_fp4_e2m1_codes(unpack_fp4(x))
     if getattr(arr, "is_fp8", False):
         return from_fp8_e4m3_bits(x)
     return from_bf16_bits(x) if getattr(arr, "is_bf16", False) or x.dtype == np.uint16 else x
@@ -440,6 +556,11 @@ class GemmBf16:
     def flops(self) -> float:
         return 2.0 * self.M * self.N * self.K
 
+    def _row_items(self) -> int:
+        """Storage items of one operand row in ``A`` / ``B``: K, one per
+        element (GemmMxFp4: K/2 bytes of two elements each)."""
+        return self.K
+
     def _group_work_items(self) -> int:
         """Work items of one tile group (``group_m`` tile rows × every tile
         column): the unit whose A rows form one contiguous panel."""
@@ -449,7 +570,7 @@ class GemmBf16:
         """Host-resident streaming needs whole tile groups (A row panels) per
         blob and an integral A panel per work item."""
         ntm, ntn = self.M // self.BM, self.N // self.BN
-        per_wi = self.BM * self.K
+        per_wi = self.BM * self._row_items()
         return (self.split_k == 1 and ntm % self.group_m == 0
                 and per_wi % (ntn * self.L) == 0)
 
@@ -480,7 +601,8 @@ class GemmBf16:
             a.read = first or not resident
         self.A.partial_read = streamed
         # an A row panel of one tile group spans group_m·BM rows; per work item
-        self.A.elements_per_work_item = (self.BM * self.K) // ((self.N // self.BN) * self.L) if streamed else 1
+        panel = self.BM * self._row_items()
+        self.A.elements_per_work_item = panel // ((self.N // self.BN) * self.L) if streamed else 1
         if self.split_k > 1:
             self.counters.read = first  # zeroed once; the kernel re-arms them
         self.C.write = not resident
@@ -513,6 +635,12 @@ class GemmBf16:
 
         arr, rows = (self.A, self.M) if name == "A" else (self.B, self.N)
         x = arr.array
+        if getattr(arr, "is_fp4", False):
+            # two e2m1 codes per byte, low nibble first, decoded by table on the device
+            p = torch.from_numpy(x).to(device)
+            codes = torch.stack((p & 15, p >> 4), dim=-1).reshape(rows, self.K).long()
+            del p
+            return torch.from_numpy(_FP4_E2M1.astype(np.float64)).to(device)[codes]
         if getattr(arr, "is_fp8", False):
             # e4m3fn bit patterns, decoded on the host (every e4m3 value is exact in bf16)
             t = torch.from_numpy(x).view(torch.float8_e4m3fn).to(torch.bfloat16).to(device)
@@ -1093,5 +1221,91 @@ class GemmMxFp8(GemmBf16):
 
     def _no_shells(self, *a, **k):
         raise NotImplementedError("GemmMxFp8 has no shell paths: the shell streamer (csrc/shell_gemm.cpp) passes no scales")
+
+    run_shells = run_host_shells = verify_shells = verify_shells_full = _no_shells
+
+
+class GemmMxFp4(GemmMxFp8):
+    """``C = (A∘SA) · (B∘SB)ᵀ`` in OCP MXFP4: e2m1 elements, two per byte,
+    with one E8M0 scale byte per 32 consecutive k, an element's value being
+    ``e2m1(code) · 2^(scale − 127)``; fp32 accumulation and output, C
+    tile-major in fragment order like :class:`GemmBf16`.
+
+    ``A`` (``M·K/2`` bytes) and ``B`` (``N·K/2`` bytes) are
+    ``ClArray(…, "float4_e2m1fn_x2")``: row-major ``[M][K/2]`` / ``[N][K/2]``,
+    element ``2i`` of a row in bits 0–3 of its byte ``i`` and element
+    ``2i + 1`` in bits 4–7 (:func:`pack_fp4`).  ``SA`` (``M·K/32``) and ``SB``
+    (``N·K/32``) are the row-major uint8 scale arrays; :func:`to_mxfp4`
+    produces both.  The kernels read the scales in the packed layout of
+    :func:`pack_mx_scales`, kept in device-side arrays of this object and
+    re-packed from ``SA`` / ``SB`` whenever the operands are uploaded, as in
+    :class:`GemmMxFp8`.
+
+    ``fill="random"`` is :class:`GemmMxFp8`'s draw (uniform [−1, 1) times
+    ``2^u`` per block, u an integer uniform in [−12, 12]) through
+    :func:`to_mxfp4`.  K must be a multiple of 256 (one K-tile of 128 bytes).
+    ``flops`` counts ``2·M·N·K`` with K in elements.  The shell paths are not
+    available, and neither is :meth:`quantize`.
+
+    Numerics: e2m1 has no NaN; a scale byte ``0xFF`` makes its block NaN
+    (OCP MX) and with it the row or column of C.  profiles/gemm_mxfp4.md has
+    what the single-instruction probe measured."""
+
+    def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
+                 cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
+                 group_m: int = 4, wave_granularity: bool | None = None):
+        BM, BN, L, kname = MXFP4_TILES[tile]
+        self.tile = tile
+        if M % BM or N % BN or K % 256 or min(M, N, K) <= 0:
+            raise ValueError(f"M%{BM}, N%{BN} and K%256 must be 0 and M, N, K positive (got {M},{N},{K})")
+        self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
+        self.geom = MXFP4_TILE_WAVES[tile]  # C tiles in fragment order
+        self.row_major_c = False
+        self.exchange = False
+        self.exchange_shift = 0
+        self.split_k = 1
+        self.tiles = (M // BM) * (N // BN)
+        self.global_range = self.tiles * L
+        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_mxfp4"))
+        self._stale = set()  # GemmMxFp8's device-quantised operands: there are none here
+        self._quantizers = {}
+        self.group_m = group_m
+        self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
+        self.dims.write = False
+        self.A = ClArray(M * K // 2, "float4_e2m1fn_x2")
+        self.B = ClArray(N * K // 2, "float4_e2m1fn_x2")
+        self.SA = ClArray(np.full(M * K // MX_BLOCK, 127, np.uint8))  # 2^0
+        self.SB = ClArray(np.full(N * K // MX_BLOCK, 127, np.uint8))
+        # the packed scales the kernels read; run() fills them from SA / SB
+        self._SAp = ClArray(np.zeros(M * K // 128, np.uint32))
+        self._SBp = ClArray(np.zeros(N * K // 128, np.uint32))
+        self.C = ClArray(M * N, np.float32)
+        for a in (self.A, self.B, self._SAp, self._SBp):
+            a.write = False
+        self.C.read = False
+        self.C.elements_per_work_item = BM * BN // L
+        self.extra = []
+        if fill == "random":
+            rng = np.random.default_rng(seed)
+            for arr, sc, rows in ((self.A, self.SA, M), (self.B, self.SB, N)):
+                x = rng.uniform(-1, 1, (rows, K // MX_BLOCK, MX_BLOCK))
+                x = np.ldexp(x, rng.integers(-12, 13, (rows, K // MX_BLOCK, 1)))
+                packed, scales = to_mxfp4(x.astype(np.float32).reshape(rows, K))
+                arr.array[:] = packed.ravel()
+                sc.array[:] = scales.ravel()
+        self._uploaded = False
+        self.wave_granularity = wave_granularity
+        self._orders = {}
+
+    def _row_items(self) -> int:
+        return self.K // 2  # bytes: two elements each
+
+    def quantize(self, *a, **k):
+        raise NotImplementedError("GemmMxFp4 takes operands quantised on the host (to_mxfp4): on-device MXFP4 "
+                                  "quantisation is a separate, later change")
+
+    def _no_shells(self, *a, **k):
+        raise NotImplementedError("GemmMxFp4 has no shell paths: the shell streamer (csrc/shell_gemm.cpp) passes no "
+                                  "scales")
 
     run_shells = run_host_shells = verify_shells = verify_shells_full = _no_shells

@@ -29,6 +29,7 @@ LIBRARY = {
                   "cek_sgemm_f32_256x256g8q"],
     "sgemm_fp8": ["cek_sgemm_fp8_128x128", "cek_sgemm_fp8_256x256pb", "cek_sgemm_fp8_256x256pbx"],
     "sgemm_mxfp8": ["cek_sgemm_mxfp8_128x128", "cek_sgemm_mxfp8_256x256pbx"],
+    "sgemm_mxfp4": ["cek_sgemm_mxfp4_128x128", "cek_sgemm_mxfp4_256x256pbx"],
     # device-side MXFP8 quantisation (ops/quantize.py): fp32 / bf16 → codes + scales, scale repack
     "mx_quantize": ["cek_mx_quantize_f32", "cek_mx_quantize_bf16", "cek_mx_pack_scales"],
     "mandelbrot": ["cek_mandelbrot_f32", "cek_mandelbrot_blk8_f32", "cek_mandelbrot_blk8h_f32",
@@ -49,6 +50,7 @@ ARITY = {
     **{k: 4 for k in LIBRARY["sgemm_f32"]},
     **{k: 4 for k in LIBRARY["sgemm_fp8"]},
     **{k: 6 for k in LIBRARY["sgemm_mxfp8"]},  # dims, A, Bt, packed SA, packed SB, C
+    **{k: 6 for k in LIBRARY["sgemm_mxfp4"]},  # the same six; A and Bt hold two e2m1 elements per byte
     **{k: 3 for k in LIBRARY["mx_quantize"]},  # X, codes, scales / dims, S, P
     **{k: 3 for k in LIBRARY["mandelbrot"]},
     **{k: 4 for k in LIBRARY["nbody"] if "energy" not in k},
