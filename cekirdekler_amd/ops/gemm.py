@@ -1147,7 +1147,15 @@ class GemmMxFp8(GemmBf16):
         e.g. another kernel of this cruncher wrote it).  ``download=True``
         also brings the codes and scales into ``A`` / ``SA`` (``B`` / ``SB``);
         otherwise the host arrays are stale until :meth:`sync_operands`."""
-        from .quantize import MxFp8Quantizer, _src_name
+        from .quantize import MxFp8Quantizer
+
+        self._quantize_with(MxFp8Quantizer, 0x4D58, name, x, src, download)
+
+    def _quantize_with(self, quantizer, base_id: int, name: str, x, src, download: bool) -> None:
+        """:meth:`quantize` with the quantizer class of the format; the
+        operand's quantise and pack computes run under ``base_id`` (A) or
+        ``base_id + 2`` (B) and the id after it."""
+        from .quantize import _src_name
 
         if name not in ("A", "B"):
             raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
@@ -1173,12 +1181,12 @@ class GemmMxFp8(GemmBf16):
             for k in [k for k in self._quantizers if k[0] == name]:  # one quantizer (and input buffer) per operand
                 del self._quantizers[k]
             codes, scales, packed = (self.A, self.SA, self._SAp) if name == "A" else (self.B, self.SB, self._SBp)
-            q = MxFp8Quantizer(rows, self.K, given, cruncher=self.cr, codes=codes, scales=scales, packed=packed,
-                               x=x if isinstance(x, ClArray) else None)
+            q = quantizer(rows, self.K, given, cruncher=self.cr, codes=codes, scales=scales, packed=packed,
+                          x=x if isinstance(x, ClArray) else None)
             self._quantizers[key] = q
         if not isinstance(x, ClArray):
             q.X.array[:] = x.reshape(-1)
-        base = 0x4D58 + (0 if name == "A" else 2)  # compute ids of the quantise and pack computes
+        base = base_id + (0 if name == "A" else 2)  # compute ids of the quantise and pack computes
         q.run(compute_id=base, upload=upload, download=download, pack_compute_id=base + 1)
         for a in (q.codes, q.scales, q.packed):
             a.read = False  # resident: the next run() must not send the host copy
@@ -1245,7 +1253,12 @@ class GemmMxFp4(GemmMxFp8):
     ``2^u`` per block, u an integer uniform in [−12, 12]) through
     :func:`to_mxfp4`.  K must be a multiple of 256 (one K-tile of 128 bytes).
     ``flops`` counts ``2·M·N·K`` with K in elements.  The shell paths are not
-    available, and neither is :meth:`quantize`.
+    available.
+
+    :meth:`quantize_operand` makes an operand from fp32 or bf16 data on the
+    devices (``kernels/mx4_quantize.hip``, the same bits as :func:`to_mxfp4`),
+    with the residency and stale-host-array rules of
+    :meth:`GemmMxFp8.quantize`; :meth:`quantize` itself is not available here.
 
     Numerics: e2m1 has no NaN; a scale byte ``0xFF`` makes its block NaN
     (OCP MX) and with it the row or column of C.  profiles/gemm_mxfp4.md has
@@ -1266,8 +1279,9 @@ class GemmMxFp4(GemmMxFp8):
         self.split_k = 1
         self.tiles = (M // BM) * (N // BN)
         self.global_range = self.tiles * L
-        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_mxfp4"))
-        self._stale = set()  # GemmMxFp8's device-quantised operands: there are none here
+        self.cr = cruncher or ClNumberCruncher(devices, "",
+                                               prebuilt=library("sgemm_mxfp4", "mx4_quantize", "mx_quantize"))
+        self._stale = set()  # operands quantised on the device whose host arrays are behind
         self._quantizers = {}
         self.group_m = group_m
         self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
@@ -1303,6 +1317,20 @@ class GemmMxFp4(GemmMxFp8):
     def quantize(self, *a, **k):
         raise NotImplementedError("GemmMxFp4 takes operands quantised on the host (to_mxfp4): on-device MXFP4 "
                                   "quantisation is a separate, later change")
+
+    def quantize_operand(self, name: str, x, src: str | None = None, download: bool = False) -> None:
+        """:meth:`GemmMxFp8.quantize` for MXFP4: quantise operand ``name``
+        from ``x`` (a float32 numpy array, bf16 bit patterns as uint16 with
+        ``src="bfloat16"``, or a float32 / bf16 :class:`ClArray` whose
+        ``read`` flag says whether it is uploaded) on the devices of this
+        GEMM's cruncher (:class:`~cekirdekler_amd.ops.quantize.MxFp4Quantizer`,
+        bit for bit :func:`to_mxfp4`, a block with a NaN getting the scale
+        byte ``0xFF``).  The packed codes, the row-major scales and the packed
+        scales stay resident for the next resident :meth:`run`; the host
+        arrays are stale until :meth:`sync_operands` unless ``download``."""
+        from .quantize import MxFp4Quantizer
+
+        self._quantize_with(MxFp4Quantizer, 0x4D60, name, x, src, download)
 
     def _no_shells(self, *a, **k):
         raise NotImplementedError("GemmMxFp4 has no shell paths: the shell streamer (csrc/shell_gemm.cpp) passes no "

@@ -32,6 +32,8 @@ LIBRARY = {
     "sgemm_mxfp4": ["cek_sgemm_mxfp4_128x128", "cek_sgemm_mxfp4_256x256pbx"],
     # device-side MXFP8 quantisation (ops/quantize.py): fp32 / bf16 → codes + scales, scale repack
     "mx_quantize": ["cek_mx_quantize_f32", "cek_mx_quantize_bf16", "cek_mx_pack_scales"],
+    # device-side MXFP4 quantisation: fp32 / bf16 → packed e2m1 codes + scales (the repack is mx_quantize's)
+    "mx4_quantize": ["cek_mx4_quantize_f32", "cek_mx4_quantize_bf16"],
     "mandelbrot": ["cek_mandelbrot_f32", "cek_mandelbrot_blk8_f32", "cek_mandelbrot_blk8h_f32",
                    "cek_mandelbrot_blk8k_f32", "cek_mandelbrot_blk8m_f32", "cek_mandelbrot_blk8t_f32",
                    "cek_mandelbrot_blk8u_f32", "cek_mandelbrot_blk8r_f32",
@@ -52,6 +54,7 @@ ARITY = {
     **{k: 6 for k in LIBRARY["sgemm_mxfp8"]},  # dims, A, Bt, packed SA, packed SB, C
     **{k: 6 for k in LIBRARY["sgemm_mxfp4"]},  # the same six; A and Bt hold two e2m1 elements per byte
     **{k: 3 for k in LIBRARY["mx_quantize"]},  # X, codes, scales / dims, S, P
+    **{k: 3 for k in LIBRARY["mx4_quantize"]},  # X, codes (two per byte), scales
     **{k: 3 for k in LIBRARY["mandelbrot"]},
     **{k: 4 for k in LIBRARY["nbody"] if "energy" not in k},
     **{k: 3 for k in LIBRARY["nbody"] if "energy" in k},

@@ -14,6 +14,11 @@ scales is contiguous, and on several devices both are gathered device to
 device so that every replica is whole.  The packed layout is K-tile-major,
 not contiguous per row slice: a second compute (one work item per packed
 dword) builds it from the whole row-major scales.
+
+MXFP4 (``kernels/mx4_quantize.hip``, :class:`MxFp4Quantizer`,
+:func:`mxfp4_reference`, :func:`mxfp4_kernel_model`) is the same machinery
+with e2m1 codes, two per byte, and :func:`cekirdekler_amd.ops.gemm.to_mxfp4`
+as the codec; its scales go through the same pack kernel.
 """
 from __future__ import annotations
 
@@ -21,10 +26,11 @@ import numpy as np
 
 from ..arrays import ClArray
 from ..cruncher import ClComputeError, ClNumberCruncher
-from .gemm import MX_BLOCK, from_bf16_bits, to_mxfp8
+from .gemm import MX_BLOCK, from_bf16_bits, pack_fp4, to_mxfp4, to_mxfp8
 from .library import LIBRARY, library
 
 QUANTIZE_KERNELS = {"float32": "cek_mx_quantize_f32", "bfloat16": "cek_mx_quantize_bf16"}
+QUANTIZE4_KERNELS = {"float32": "cek_mx4_quantize_f32", "bfloat16": "cek_mx4_quantize_bf16"}
 PACK_KERNEL = "cek_mx_pack_scales"
 LOCAL = 64  # work items (= blocks) per work-group
 _SRC_NAMES = {"float32": "float32", "float": "float32", "f32": "float32", "bfloat16": "bfloat16", "bf16": "bfloat16"}
@@ -62,6 +68,26 @@ def e4m3_convert_model(y: np.ndarray) -> np.ndarray:
     return np.where(c < np.uint32(0x3C800000), sub, norm) | s
 
 
+def _model_blocks(x, src: str) -> tuple:
+    """The kernel models' common start: ``x`` as uint32 bit patterns in blocks
+    of 32 (``[blocks][32]``), their keys ``|x| bits + 2^23`` as int32, and per
+    block the bits of the finite |x| maximum (0 where nothing is finite)."""
+    src = _src_name(src)
+    x = np.asarray(x)
+    if src == "bfloat16":
+        if x.dtype != np.uint16:
+            raise ValueError("bfloat16 input is given as uint16 bit patterns")
+        u = x.astype(np.uint32) << np.uint32(16)
+    else:
+        u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    if u.shape[-1] % MX_BLOCK:
+        raise ValueError(f"the last axis ({u.shape[-1]}) must be a multiple of the block ({MX_BLOCK})")
+    ub = np.ascontiguousarray(u).reshape(-1, MX_BLOCK)
+    key = ((ub & np.uint32(0x7FFFFFFF)) + np.uint32(0x00800000)).view(np.int32)
+    amax = (np.maximum(key.max(axis=1), np.int32(0x00800000)) - np.int32(0x00800000)).astype(np.uint32)
+    return x, ub, key, amax
+
+
 def mxfp8_kernel_model(x, src: str = "float32") -> tuple:
     """``kernels/mx_quantize.hip`` step by step, in uint32 and float32
     operations only.  Per block: the maximum of the keys ``|x| bits + 2^23``
@@ -77,19 +103,7 @@ def mxfp8_kernel_model(x, src: str = "float32") -> tuple:
     float32 values, or bf16 bit patterns (uint16) with ``src="bfloat16"``;
     blocks of 32 along the last axis.  Returns ``(codes uint8 like x, scales
     uint8 [..., K/32])``."""
-    src = _src_name(src)
-    x = np.asarray(x)
-    if src == "bfloat16":
-        if x.dtype != np.uint16:
-            raise ValueError("bfloat16 input is given as uint16 bit patterns")
-        u = x.astype(np.uint32) << np.uint32(16)
-    else:
-        u = np.ascontiguousarray(x, np.float32).view(np.uint32)
-    if u.shape[-1] % MX_BLOCK:
-        raise ValueError(f"the last axis ({u.shape[-1]}) must be a multiple of the block ({MX_BLOCK})")
-    ub = np.ascontiguousarray(u).reshape(-1, MX_BLOCK)
-    key = ((ub & np.uint32(0x7FFFFFFF)) + np.uint32(0x00800000)).view(np.int32)
-    amax = (np.maximum(key.max(axis=1), np.int32(0x00800000)) - np.int32(0x00800000)).astype(np.uint32)
+    x, ub, key, amax = _model_blocks(x, src)
     field = (amax >> np.uint32(23)).astype(np.int32)
     sb = np.where(amax == 0, 127, np.maximum(field - 8, 0)).astype(np.uint32)
     mult = ((np.uint32(254) - sb) << np.uint32(23)).view(np.float32)
@@ -101,22 +115,70 @@ def mxfp8_kernel_model(x, src: str = "float32") -> tuple:
     return codes.astype(np.uint8).reshape(x.shape), sb.astype(np.uint8).reshape(x.shape[:-1] + (-1,))
 
 
+def mxfp4_reference(x) -> tuple:
+    """What the MXFP4 quantise kernels compute: :func:`to_mxfp4` of the
+    float32 input, or of the decoded values of bf16 bit patterns (a uint16
+    array or a bf16 :class:`ClArray`): ``(packed codes [..., K/2], scales)``,
+    blocks along the last axis."""
+    if isinstance(x, ClArray):
+        x = x.array
+    x = np.asarray(x)
+    return to_mxfp4(from_bf16_bits(x) if x.dtype == np.uint16 else x.astype(np.float32, copy=False))
+
+
+def e2m1_convert_model(y: np.ndarray) -> np.ndarray:
+    """gfx950's fp4 conversion of float32 ``y`` as the GPU tier found it
+    (profiles/quantize_mxfp4.md), uint32 codes 0..15 under the sign of ``y``:
+    round to nearest even at one mantissa bit, below 1 in units of 0.5, and
+    whatever lies beyond 6, inf and NaN included, as the largest code 7."""
+    u = np.ascontiguousarray(y, np.float32).view(np.uint32)
+    a = u & np.uint32(0x7FFFFFFF)
+    s = (u >> np.uint32(28)) & np.uint32(8)
+    c = np.minimum(a, np.uint32(0x40C00000))  # 6
+    norm = ((c + np.uint32(0x1FFFFF) + ((c >> np.uint32(22)) & np.uint32(1))) >> np.uint32(22)) - np.uint32(126 << 1)
+    sub = (c.view(np.float32) * np.float32(2.0) + np.float32(8388608.0)).view(np.uint32) & np.uint32(3)
+    return np.where(c < np.uint32(0x3F800000), sub, norm) | s
+
+
+def mxfp4_kernel_model(x, src: str = "float32") -> tuple:
+    """``kernels/mx4_quantize.hip`` step by step, in uint32 and float32
+    operations only.  Per block: the maximum of the keys as in
+    :func:`mxfp8_kernel_model`, the scale byte ``max(E − 2, 0)`` from that
+    maximum's exponent field E (127 when it is zero or nothing is finite).
+    Per element: the conversion of ``x · 2^-e`` (:func:`e2m1_convert_model`;
+    one float32 multiply by ``2^-e``, bits ``(254 − byte) << 23``, always a
+    normal number — the product is exact unless it underflows, far below
+    e2m1's round-to-zero boundary 0.25, where the code is a signed zero), then
+    the NaN rule: a NaN element gets code 0 without a sign and its block the
+    byte ``0xFF``, the block's other elements keep their codes.  ``x``:
+    float32 values, or bf16 bit patterns (uint16) with ``src="bfloat16"``;
+    blocks of 32 along the last axis.  Returns ``(packed codes uint8 [...,
+    K/2], scales uint8 [..., K/32])`` like :func:`to_mxfp4`."""
+    x, ub, key, amax = _model_blocks(x, src)
+    field = (amax >> np.uint32(23)).astype(np.int32)
+    sb = np.where(amax == 0, 127, np.maximum(field - 2, 0)).astype(np.uint32)
+    mult = ((np.uint32(254) - sb) << np.uint32(23)).view(np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        w = e2m1_convert_model(ub.view(np.float32) * mult[:, None])
+    nan = (np.uint32(0x80000000) - key.view(np.uint32)).view(np.int32) < 0
+    codes = np.where(nan, np.uint32(0), w).astype(np.uint8).reshape(x.shape)
+    sb = np.where(nan.any(axis=1), np.uint32(0xFF), sb)
+    return pack_fp4(codes), sb.astype(np.uint8).reshape(x.shape[:-1] + (-1,))
+
+
 _FLAGS = ("read", "partial_read", "write", "elements_per_work_item", "gather_resident")
 
 
-class MxFp8Quantizer:
-    """``[rows][K]`` fp32 or bf16 → MXFP8 through ``compute()``.
+class _MxQuantizer:
+    """What :class:`MxFp8Quantizer` and :class:`MxFp4Quantizer` share: the
+    argument checks, the arrays and the two computes.  A format names its
+    quantise kernels, the libraries they and the pack kernel come from, the
+    dtype of its codes and how many elements a code byte holds."""
 
-    ``X`` (``rows·K`` of the source type; bf16 as the uint16-storage bf16
-    ClArray) is the input, ``codes`` (``"float8_e4m3fn"``), ``scales`` (uint8,
-    ``rows·K/32``, row-major) and ``packed`` (uint32, ``rows·K/128``, the
-    layout of :func:`~cekirdekler_amd.ops.gemm.pack_mx_scales`) the outputs;
-    ``packed`` exists when rows % 64 = 0 and K % 128 = 0 and is None
-    otherwise.  Arrays passed in are adopted (``x``: an input that already
-    lives in a ClArray, e.g. another kernel's output); their transfer flags
-    are as they were when :meth:`run` returns.
-
-    The number of blocks ``rows·K/32`` must be a multiple of 64."""
+    KERNELS: dict
+    LIBS: tuple
+    CODES_DTYPE: str
+    PER_BYTE = 1
 
     def __init__(self, rows: int, K: int, src: str = "float32", devices=None,
                  cruncher: ClNumberCruncher | None = None, codes: ClArray | None = None,
@@ -129,11 +191,11 @@ class MxFp8Quantizer:
         self.blocks = rows * K // MX_BLOCK
         if self.blocks % LOCAL:
             raise ValueError(f"the number of blocks rows*K/{MX_BLOCK} ({self.blocks}) must be a multiple of {LOCAL}")
-        self.kernel = QUANTIZE_KERNELS[self.src]
+        self.kernel = self.KERNELS[self.src]
         self.has_packed = rows % 64 == 0 and K % 128 == 0
         n = rows * K
         want = [("x", x, n, np.float32 if self.src == "float32" else np.uint16),
-                ("codes", codes, n, np.uint8), ("scales", scales, self.blocks, np.uint8)]
+                ("codes", codes, n // self.PER_BYTE, np.uint8), ("scales", scales, self.blocks, np.uint8)]
         if self.has_packed:
             want.append(("packed", packed, n // 128, np.uint32))
         elif packed is not None:
@@ -141,14 +203,15 @@ class MxFp8Quantizer:
         for name, arr, length, dt in want:
             if arr is not None and (not isinstance(arr, ClArray) or arr.N != length or arr.array.dtype != dt):
                 raise ValueError(f"{name} must be a ClArray of {length} {np.dtype(dt).name} elements")
-        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("mx_quantize"))
+        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library(*self.LIBS))
         have = {k.split(":")[0] for k in self.cr.kernel_names}
-        missing = [k for k in LIBRARY["mx_quantize"] if k not in have]
-        if missing:
-            raise ClComputeError(f"the cruncher has no kernel {missing[0]!r}: it was built without "
-                                 "library('mx_quantize')")
+        for lib in self.LIBS:
+            missing = [k for k in LIBRARY[lib] if k not in have]
+            if missing:
+                raise ClComputeError(f"the cruncher has no kernel {missing[0]!r}: it was built without "
+                                     f"library({lib!r})")
         self.X = x if x is not None else ClArray(n, "float32" if self.src == "float32" else "bfloat16")
-        self.codes = codes if codes is not None else ClArray(n, "float8_e4m3fn")
+        self.codes = codes if codes is not None else ClArray(n // self.PER_BYTE, self.CODES_DTYPE)
         self.scales = scales if scales is not None else ClArray(self.blocks, np.uint8)
         self.packed = None
         if self.has_packed:
@@ -174,7 +237,7 @@ class MxFp8Quantizer:
         gather = self.cr.number_of_devices > 1
         try:
             for a, epw, rd, wr, ga in ((self.X, MX_BLOCK, upload, False, False),
-                                       (self.codes, MX_BLOCK, False, download, gather),
+                                       (self.codes, MX_BLOCK // self.PER_BYTE, False, download, gather),
                                        (self.scales, 1, False, download, gather)):
                 a.partial_read = False
                 a.read, a.write, a.elements_per_work_item, a.gather_resident = rd, wr, epw, ga
@@ -195,3 +258,37 @@ class MxFp8Quantizer:
             for a, flags in saved:
                 for f, v in zip(_FLAGS, flags):
                     setattr(a, f, v)
+
+
+class MxFp8Quantizer(_MxQuantizer):
+    """``[rows][K]`` fp32 or bf16 → MXFP8 through ``compute()``.
+
+    ``X`` (``rows·K`` of the source type; bf16 as the uint16-storage bf16
+    ClArray) is the input, ``codes`` (``"float8_e4m3fn"``), ``scales`` (uint8,
+    ``rows·K/32``, row-major) and ``packed`` (uint32, ``rows·K/128``, the
+    layout of :func:`~cekirdekler_amd.ops.gemm.pack_mx_scales`) the outputs;
+    ``packed`` exists when rows % 64 = 0 and K % 128 = 0 and is None
+    otherwise.  Arrays passed in are adopted (``x``: an input that already
+    lives in a ClArray, e.g. another kernel's output); their transfer flags
+    are as they were when :meth:`run` returns.
+
+    The number of blocks ``rows·K/32`` must be a multiple of 64."""
+
+    KERNELS = QUANTIZE_KERNELS
+    LIBS = ("mx_quantize",)
+    CODES_DTYPE = "float8_e4m3fn"
+
+
+class MxFp4Quantizer(_MxQuantizer):
+    """``[rows][K]`` fp32 or bf16 → MXFP4 through ``compute()``
+    (``kernels/mx4_quantize.hip``), bit for bit
+    :func:`~cekirdekler_amd.ops.gemm.to_mxfp4`: :class:`MxFp8Quantizer` with
+    ``codes`` a ``"float4_e2m1fn_x2"`` array of ``rows·K/2`` bytes (two
+    elements per byte, :func:`~cekirdekler_amd.ops.gemm.pack_fp4`).  A block
+    with a NaN has the scale byte ``0xFF``.  The pack compute is the MXFP8
+    one, so the cruncher needs ``library("mx4_quantize", "mx_quantize")``."""
+
+    KERNELS = QUANTIZE4_KERNELS
+    LIBS = ("mx4_quantize", "mx_quantize")
+    CODES_DTYPE = "float4_e2m1fn_x2"
+    PER_BYTE = 2
