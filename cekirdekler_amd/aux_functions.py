@@ -28,7 +28,7 @@ __device__ inline unsigned short cek_f32_to_bf16(float f) {   // round to neares
   unsigned int r = 0x7fffu + ((c.u >> 16) & 1u);
   return (unsigned short)((c.u + r) >> 16); }
 """,
-    # OCP e4m3fn (the codec of ops/gemm.py: round to nearest even, subnormals
+    # OCP e4m3fn (the codec of ops/codecs.py: round to nearest even, subnormals
     # of 2^-9 kept, finite values beyond 448 saturate, NaN = 0x7f)
     "fp8": r"""
 __device__ inline float cek_fp8_e4m3_to_f32(unsigned char h) {

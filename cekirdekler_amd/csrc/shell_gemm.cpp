@@ -17,7 +17,7 @@
 // main (upload) stream, two compute streams and two download streams.
 //
 // Host C layout: shell by shell, R_s then C_s, each tile-major in the
-// kernel's grouped tile order (ops/gemm.py untiles it).
+// kernel's grouped tile order (ops/tiling.py untiles it).
 #include <algorithm>
 #include <cstring>
 #include <string>

@@ -1,7 +1,7 @@
 // MXFP4 quantisation on the device (HBM-bound): fp32 or bf16 in, OCP e2m1
 // codes (two per byte: element 2i in bits 0-3 of byte i, element 2i + 1 in
 // bits 4-7) plus one E8M0 scale byte per block of 32 consecutive elements
-// out, bit for bit what ops/gemm.py's to_mxfp4 computes.  The repack of the
+// out, bit for bit what ops/codecs.py's to_mxfp4 computes.  The repack of the
 // row-major scale bytes into the dwords the GEMM kernels read is
 // mx_quantize.hip's cek_mx_pack_scales, which does not look at the bytes.
 //
@@ -35,64 +35,28 @@
 // The group's 64 scale bytes are collected with four ds_bpermute into lanes
 // 0..15 and stored as 16 dwords.  No LDS.
 #include "cek_kernel.h"
-
-typedef unsigned int u32;
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float mx4q_float(u32 u) { return __builtin_bit_cast(float, u); }
-
-// |x| bits + 2^23 as a signed int: finite values stay positive and keep their
-// order, inf is INT_MIN and NaN lies above it, so a signed max is the maximum
-// over the finite values wherever there is one
-__device__ __forceinline__ int mx4q_key(u32 u) { return (int)((u & 0x7fffffffu) + 0x00800000u); }
+#include "mx_quantize_parts.h"
 
 // 0xF in nibble `k` for the key of a NaN, else 0
 __device__ __forceinline__ u32 mx4q_nan_nibble(int key, int k) {
   return (u32)((int)(0x80000000u - (u32)key) >> 31) & (0xFu << (4 * k));
 }
 
-// max / OR over the four lanes of a block (aligned quads), in every lane:
-// quad_perm [1,0,3,2], then quad_perm [2,3,0,1]
-__device__ __forceinline__ int mx4q_block_max(int m) {
-  m = max(m, __builtin_amdgcn_update_dpp(0, m, 0xB1, 0xF, 0xF, true));
-  return max(m, __builtin_amdgcn_update_dpp(0, m, 0x4E, 0xF, 0xF, true));
-}
-
+// OR over the four lanes of a block (aligned quads), in every lane: quad_perm
+// [1,0,3,2], then quad_perm [2,3,0,1]
 __device__ __forceinline__ u32 mx4q_block_or(u32 m) {
   m |= (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true);
   return m | (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true);
-}
-
-// scale byte e + 127 from a block's maximum key: e = max(E - 129, -127) with E
-// the exponent field of the finite |x| maximum, e = 0 when that is 0 or no
-// element is finite
-__device__ __forceinline__ u32 mx4q_scale_byte(int key) {
-  const u32 amax = (u32)max(key, 0x00800000) - 0x00800000u;
-  return amax == 0u ? 127u : (u32)max((int)(amax >> 23) - 2, 0);
-}
-
-// The group's 64 scale bytes as 16 dwords.  `mine` is, in every lane, the
-// scale byte of the block this lane's quad had in step (lane % 4).  Dword j,
-// byte b is block 4j + b: step (4j + b) / 16, quad (4j + b) % 16.
-__device__ __forceinline__ void mx4q_store_scales(u32 mine, u32* scales32, long long group, int lane) {
-  const int j = lane & 15;
-  u32 w = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int blk = 4 * j + b, src = (blk % 16) * 4 + blk / 16;
-    w |= (u32)__builtin_amdgcn_ds_bpermute(src << 2, (int)mine) << (8 * b);
-  }
-  if (lane < 16) scales32[group * 16 + lane] = w;
 }
 
 // eight fp32 bit patterns scaled by 2^-e (`scale` = 2^e) and rounded to e2m1:
 // element i in nibble i
 __device__ __forceinline__ u32 mx4q_cvt8(const u32 (&f)[8], float scale) {
   u32 w = 0;
-  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx4q_float(f[0]), mx4q_float(f[1]), scale, 0);
-  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx4q_float(f[2]), mx4q_float(f[3]), scale, 1);
-  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx4q_float(f[4]), mx4q_float(f[5]), scale, 2);
-  return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mx4q_float(f[6]), mx4q_float(f[7]), scale, 3);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mxq_float(f[0]), mxq_float(f[1]), scale, 0);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mxq_float(f[2]), mxq_float(f[3]), scale, 1);
+  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mxq_float(f[4]), mxq_float(f[5]), scale, 2);
+  return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mxq_float(f[6]), mxq_float(f[7]), scale, 3);
 }
 
 // the byte the block stores: 0xFF when one of its elements is a NaN
@@ -118,18 +82,18 @@ extern "C" __global__ __launch_bounds__(64) void cek_mx4_quantize_f32(const u32x
     u32 nan = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const int key = mx4q_key(f[i]);
+      const int key = mxq_key(f[i]);
       m = max(m, key);
       nan |= mx4q_nan_nibble(key, i);
     }
-    const u32 sb = mx4q_scale_byte(mx4q_block_max(m));
-    const float scale = mx4q_float(sb << 23);  // 2^e, e = sb - 127
+    const u32 sb = mxq_scale_byte<2>(mxq_block_max<4>(m));
+    const float scale = mxq_float(sb << 23);  // 2^e, e = sb - 127
     const u32 w = mx4q_cvt8(f, scale);
     codes[base + s * 64] = w & ~nan;
     const u32 stored = mx4q_stored_byte(sb, nan);
     mine = (lane & 3) == s ? stored : mine;
   }
-  mx4q_store_scales(mine, scales, group, lane);
+  mxq_store_scales<4>(mine, scales, group, lane);
 }
 
 extern "C" __global__ __launch_bounds__(64) void cek_mx4_quantize_bf16(const u32x4* x, u32* codes, u32* scales,
@@ -154,16 +118,16 @@ extern "C" __global__ __launch_bounds__(64) void cek_mx4_quantize_bf16(const u32
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      const int key = mx4q_key(f[i]);
+      const int key = mxq_key(f[i]);
       m = max(m, key);
       nan |= mx4q_nan_nibble(key, i);
     }
-    const u32 sb = mx4q_scale_byte(mx4q_block_max(m));
-    const float scale = mx4q_float(sb << 23);
+    const u32 sb = mxq_scale_byte<2>(mxq_block_max<4>(m));
+    const float scale = mxq_float(sb << 23);
     const u32 w = mx4q_cvt8(f, scale);
     codes[base + s * 64] = w & ~nan;
     const u32 stored = mx4q_stored_byte(sb, nan);
     mine = (lane & 3) == s ? stored : mine;
   }
-  mx4q_store_scales(mine, scales, group, lane);
+  mxq_store_scales<4>(mine, scales, group, lane);
 }

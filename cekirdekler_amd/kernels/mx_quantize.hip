@@ -1,6 +1,6 @@
 // MXFP8 quantisation on the device (HBM-bound): fp32 or bf16 in, OCP e4m3fn
 // codes plus one E8M0 scale byte per block of 32 consecutive elements out,
-// bit for bit what ops/gemm.py's to_mxfp8 computes, and the repack of the
+// bit for bit what ops/codecs.py's to_mxfp8 computes, and the repack of the
 // row-major scale bytes into the dwords the MXFP8 GEMM kernels read
 // (sgemm_mxfp8.hip, pack_mx_scales).
 //
@@ -32,41 +32,14 @@
 // is S[g·64 + b·16 + l % 16][kt·4 + l / 16].  Lane l loads the dword
 // S[g·64 + l][kt·4 .. kt·4 + 3]; four ds_bpermute transpose the 64 × 4 bytes.
 #include "cek_kernel.h"
+#include "mx_quantize_parts.h"
 
-typedef unsigned int u32;
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float mxq_float(u32 u) { return __builtin_bit_cast(float, u); }
-
-// |x| bits + 2^23 as a signed int: finite values stay positive and keep their
-// order, inf is INT_MIN and NaN lies above it, so a signed max is the maximum
-// over the finite values wherever there is one
-__device__ __forceinline__ int mxq_key(u32 u) { return (int)((u & 0x7fffffffu) + 0x00800000u); }
 
 // 0x80 in byte `k` for the key of a NaN, else 0
 __device__ __forceinline__ u32 mxq_nan_bit(int key, int k) {
   return (u32)((int)(0x80000000u - (u32)key) >> 31) & (0x80u << (8 * k));
-}
-
-// max over the LPB lanes of a block (LPB-aligned lane groups), in every lane
-template <int LPB>
-__device__ __forceinline__ int mxq_block_max(int m) {
-  // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror (lane i <-> 7 - i
-  // of each 8, equal quads by then)
-  m = max(m, __builtin_amdgcn_update_dpp(0, m, 0xB1, 0xF, 0xF, true));
-  m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x4E, 0xF, 0xF, true));
-  if (LPB == 8) m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x141, 0xF, 0xF, true));
-  return m;
-}
-
-// scale byte e + 127 from a block's maximum key: e = max(E - 135, -127) with E
-// the exponent field of the finite |x| maximum, e = 0 when that is 0 or no
-// element is finite
-__device__ __forceinline__ u32 mxq_scale_byte(int key) {
-  const u32 amax = (u32)max(key, 0x00800000) - 0x00800000u;
-  return amax == 0u ? 127u : (u32)max((int)(amax >> 23) - 8, 0);
 }
 
 // The conversion's dword made the codec's.  Bytes whose low seven bits are all
@@ -85,23 +58,6 @@ __device__ __forceinline__ u32 mxq_cvt4(float a, float b, float c, float d, floa
   return __builtin_bit_cast(u32, r);
 }
 
-// The group's 64 scale bytes as 16 dwords.  `mine` is, in every lane, the
-// scale byte of the block this lane's group had in step (lane % LPB).  Dword
-// j, byte b is block 4j + b: step (4j + b) / GPS, lane group (4j + b) % GPS,
-// GPS = 64 / LPB groups per step.
-template <int LPB>
-__device__ __forceinline__ void mxq_store_scales(u32 mine, u32* scales32, long long group, int lane) {
-  constexpr int GPS = 64 / LPB;
-  const int j = lane & 15;
-  u32 w = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int blk = 4 * j + b, src = (blk % GPS) * LPB + blk / GPS;
-    w |= (u32)__builtin_amdgcn_ds_bpermute(src << 2, (int)mine) << (8 * b);
-  }
-  if (lane < 16) scales32[group * 16 + lane] = w;
-}
-
 extern "C" __global__ __launch_bounds__(64) void cek_mx_quantize_f32(const u32x4* x, u32* codes, u32* scales,
                                                                       CEK_HIDDEN) {
   const int lane = (int)threadIdx.x;
@@ -115,7 +71,7 @@ extern "C" __global__ __launch_bounds__(64) void cek_mx_quantize_f32(const u32x4
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     const int k0 = mxq_key(v[s].x), k1 = mxq_key(v[s].y), k2 = mxq_key(v[s].z), k3 = mxq_key(v[s].w);
-    const u32 sb = mxq_scale_byte(mxq_block_max<8>(max(max(k0, k1), max(k2, k3))));
+    const u32 sb = mxq_scale_byte<8>(mxq_block_max<8>(max(max(k0, k1), max(k2, k3))));
     const u32 nan = mxq_nan_bit(k0, 0) | mxq_nan_bit(k1, 1) | mxq_nan_bit(k2, 2) | mxq_nan_bit(k3, 3);
     const float scale = mxq_float(sb << 23);  // 2^e, e = sb - 127
     codes[base + s * 64] = mxq_fix(
@@ -151,7 +107,7 @@ extern "C" __global__ __launch_bounds__(64) void cek_mx_quantize_bf16(const u32x
       m = max(m, key);
       nan[i >> 2] |= mxq_nan_bit(key, i & 3);
     }
-    const u32 sb = mxq_scale_byte(mxq_block_max<4>(m));
+    const u32 sb = mxq_scale_byte<8>(mxq_block_max<4>(m));
     const float scale = mxq_float(sb << 23);
     u32x2 c;
     c.x = mxq_fix(mxq_cvt4(mxq_float(f[0]), mxq_float(f[1]), mxq_float(f[2]), mxq_float(f[3]), scale), nan.x);

@@ -4,7 +4,7 @@
 //   C = A · Bᵀ      A: [M][K] bf16 row-major, Bt: [N][K] bf16 row-major
 //   C is written TILE-MAJOR: tile t = (tm, tn) (tn fastest) occupies
 //   C[t·BM·BN ...] in MFMA-fragment order inside the tile (epilogue; the
-//   host's ops/gemm.py tile_to_rows restores rows), so any contiguous range of
+//   host's ops/tiling.py tile_to_rows restores rows), so any contiguous range of
 //   tiles — the slice a device gets from the load balancer — is one
 //   contiguous byte range (the reference's partial write of
 //   [ref·e, (ref+r)·e), Worker.cs:1349-1352, with e = BM·BN / local).
@@ -596,7 +596,7 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
   // C tile in fragment order: wave (wr, wc)'s fragment (i, j) is 64 lanes ×
   // 16 B = 1 KiB contiguous, so every store is one dwordx4 per lane (a
   // row-major tile takes four dword stores per fragment, and with one
-  // work-group per CU the store tail is exposed).  Host side: ops/gemm.py
+  // work-group per CU the store tail is exposed).  Host side: ops/tiling.py
   // tile_to_rows.  Element (row, col) of the tile lives at
   // ((((wr·WN + wc)·FM + i)·FN + j)·64 + fq·16 + fr)·4 + r.
   if constexpr (ROWC) {

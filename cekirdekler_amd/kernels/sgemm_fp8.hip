@@ -3,7 +3,7 @@
 //
 //   C = A · Bᵀ      A: [M][K] e4m3fn row-major, Bt: [N][K] e4m3fn row-major
 //   C is written TILE-MAJOR in MFMA-fragment order, exactly as the bf16
-//   kernels write it (ops/gemm.py tile_to_rows restores rows), one work-group
+//   kernels write it (ops/tiling.py tile_to_rows restores rows), one work-group
 //   per BM×BN tile, dims = the bf16 kernels' 8 words.
 //
 // The byte geometry is the bf16 kernels' (gemm_parts.h at ESZ = 1): LDS rows

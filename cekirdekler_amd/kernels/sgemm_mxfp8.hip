@@ -52,7 +52,7 @@
 //     byte i (bits 8i .. 8i+7) = SA[g·64 + i·16 + l % 16][kt·4 + l / 16]
 //   dword index = (kt · M/64 + g)·64 + l; SBp the same from SB with N for M.
 //
-// (ops/gemm.py pack_mx_scales / unpack_mx_scales; private to that file and
+// (ops/tiling.py pack_mx_scales / unpack_mx_scales; private to that file and
 // this one.)  A wave whose rows start at 64·g reads dword g + d for fragments
 // 4d .. 4d+3 and issues fragment i with op_sel = i & 3 (op_sel = b picks bits
 // 8b .. 8b+7, checked by the same probe): one coalesced 256-B

@@ -13,6 +13,10 @@ devices in whole tiles and each device's C slice is one contiguous range
 leaves C in device memory (the BASELINE "device-resident" number);
 ``resident=False`` is the reference's host-resident semantics: A and B are
 uploaded and every device downloads its C slice on each call.
+
+The element codecs live in ``ops/codecs.py`` and the C-tile and scale layouts
+in ``ops/tiling.py``; both are imported here by name, so this module remains
+the import path for all of them.
 """
 from __future__ import annotations
 
@@ -20,7 +24,12 @@ import numpy as np
 
 from ..arrays import ClArray
 from ..cruncher import ClComputeError, ClNumberCruncher
+from .codecs import (FP4_E2M1_EMAX, MX_BLOCK, e8m0_to_f64, from_bf16_bits, from_fp4_e2m1_codes,  # noqa: F401
+                     from_fp8_e4m3_bits, from_mxfp4, from_mxfp8, pack_fp4, to_bf16_bits, to_fp4_e2m1_codes,
+                     to_fp8_e4m3_bits, to_mxfp4, to_mxfp8, unpack_fp4)
 from .library import library
+from .quantize import MxFp4Quantizer, MxFp8Quantizer, _src_name
+from .tiling import pack_mx_scales, rows_to_tile, tile_coords, tile_to_rows, unpack_mx_scales, untile  # noqa: F401
 
 # tile name -> (BM, BN, work-group size, kernel).  The production tiles and
 # at most two tested alternates per dtype; every variant measured and dropped
@@ -70,27 +79,6 @@ TILE_WAVES = {
     "256x128pe": (4, 2, 4, 4), "256x128pb": (4, 2, 4, 4), "128x128": (2, 2, 4, 4),
 }
 
-
-def tile_to_rows(t: np.ndarray, geom) -> np.ndarray:
-    """Fragment-ordered C tiles (``[..., BM·BN]``) → row-major ``[..., BM, BN]``.
-    In-tile offset of (row, col) = ((((wr·WN + wc)·FM + i)·FN + j)·64 + fq·16 + fr)·4 + r
-    with row = wr·16FM + i·16 + fq·4 + r and col = wc·16FN + j·16 + fr."""
-    WM, WN, FM, FN = geom
-    lead = t.shape[:-1]
-    x = t.reshape(lead + (WM, WN, FM, FN, 4, 16, 4))
-    n = len(lead)
-    perm = list(range(n)) + [n + 0, n + 2, n + 4, n + 6, n + 1, n + 3, n + 5]
-    return x.transpose(perm).reshape(lead + (WM * FM * 16, WN * FN * 16))
-
-
-def rows_to_tile(b: np.ndarray, geom) -> np.ndarray:
-    """Inverse of :func:`tile_to_rows`: row-major ``[..., BM, BN]`` → fragment order."""
-    WM, WN, FM, FN = geom
-    lead = b.shape[:-2]
-    x = b.reshape(lead + (WM, FM, 4, 4, WN, FN, 16))  # wr i fq r wc j fr
-    n = len(lead)
-    perm = list(range(n)) + [n + 0, n + 4, n + 1, n + 5, n + 2, n + 6, n + 3]
-    return np.ascontiguousarray(x.transpose(perm)).reshape(lead + (-1,))
 
 # fp32 tiles (kernels/sgemm_f32.hip): v_mfma_f32_16x16x4_f32, BK = 32
 F32_TILES = {
@@ -157,7 +145,6 @@ MXFP8_TILES = {
     "128x128": (128, 128, 256, "cek_sgemm_mxfp8_128x128"),
 }
 MXFP8_TILE_WAVES = {"256x256pbx": (2, 4, 8, 4), "128x128": (2, 2, 4, 4)}
-MX_BLOCK = 32  # elements per scale along K
 
 # MXFP4 tiles (kernels/sgemm_mxfp4.hip): the MXFP8 structures with e2m1
 # operands, two per byte, a K-tile of 128 B = 256 k as two scaled
@@ -183,218 +170,6 @@ EXCHANGE_TILES = {"256x256pbw": 4, "256x256pbh": 4, "256x256pbs": 4}
 EXCHANGE_SHIFT = {"256x256pbw": 4, "256x256pbh": 4, "256x256pbs": 0}
 
 
-def to_bf16_bits(x: np.ndarray) -> np.ndarray:
-    """fp32 → bf16 bit patterns (round to nearest even), as uint16.  A NaN
-    stays a NaN: its sign and top 7 payload bits are kept and the quiet bit is
-    set (the rounding increment would carry a NaN with a low payload into
-    ±Inf or ±0)."""
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
-    return np.where(nan, ((u >> 16) | np.uint32(0x0040)).astype(np.uint16), r)
-
-
-def from_bf16_bits(b: np.ndarray) -> np.ndarray:
-    return (b.astype(np.uint32) << 16).view(np.float32)
-
-
-def _fp8_e4m3_table() -> np.ndarray:
-    c = np.arange(256)
-    e, m = (c >> 3) & 15, (c & 7).astype(np.float64)
-    v = np.where(e == 0, m * 2.0 ** -9, (1 + m / 8) * 2.0 ** (e - 7.0))
-    v[(c & 0x7F) == 0x7F] = np.nan
-    return np.where(c & 0x80, -v, v).astype(np.float32)
-
-
-_FP8_E4M3 = _fp8_e4m3_table()
-
-
-def to_fp8_e4m3_bits(x: np.ndarray) -> np.ndarray:
-    """fp32 → OCP e4m3fn bit patterns, as uint8: round to nearest even
-    (subnormals included: the smallest is 2⁻⁹), NaN → ``0x7F``, the sign of
-    zero kept.  Finite values beyond ±448 and ±inf SATURATE to ±448
-    (``0x7E`` / ``0xFE``); torch's CPU conversion turns what rounds past 448
-    into NaN instead, and agrees bit for bit everywhere else."""
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
-    a = u & np.uint32(0x7FFFFFFF)
-    sign = ((u >> 24) & np.uint32(0x80)).astype(np.uint8)
-    # normal range: nearest even at 3 mantissa bits, exponent rebiased 127 → 7
-    norm = ((a + np.uint32(0x7FFFF) + ((a >> 20) & np.uint32(1))) >> 20).astype(np.int64) - (120 << 3)
-    # below 2⁻⁶: units of 2⁻⁹ (8 units = code 0x08 = 2⁻⁶, the first normal)
-    small = a < np.uint32(0x3C800000)
-    sub = np.rint(np.where(small, a, np.uint32(0)).view(np.float32) * np.float32(512.0)).astype(np.int64)
-    code = np.where(small, sub, norm)
-    code = np.where(a >= np.uint32(0x43E00000), 0x7E, code).astype(np.uint8) | sign  # |x| >= 448, inf
-    return np.where(a > np.uint32(0x7F800000), np.uint8(0x7F), code).astype(np.uint8)
-
-
-def from_fp8_e4m3_bits(b: np.ndarray) -> np.ndarray:
-    """OCP e4m3fn bit patterns (uint8) → fp32 (``0x7F`` / ``0xFF`` → NaN)."""
-    return _FP8_E4M3[np.asarray(b, dtype=np.uint8)]
-
-
-def e8m0_to_f64(scales: np.ndarray) -> np.ndarray:
-    """E8M0 scale bytes → float64 ``2^(byte − 127)``, exact (``0xFF`` → NaN)."""
-    s = np.asarray(scales, dtype=np.uint8)
-    return np.where(s == 0xFF, np.nan, np.ldexp(1.0, s.astype(np.int64) - 127))
-
-
-def to_mxfp8(x: np.ndarray, block: int = MX_BLOCK):
-    """OCP Microscaling (MX v1.0) MXFP8 along the last axis: ``(codes uint8
-    [..., K], scales uint8 [..., K/block])``.  Per block the shared exponent is
-    ``e = floor(log2(max |x| over the block's finite values)) − 8`` (8: the
-    exponent of e4m3's largest binade), clamped to [−127, 127], the scale byte
-    ``e + 127`` and the elements ``to_fp8_e4m3_bits(x · 2^−e)``: round to
-    nearest even, saturating, so scaled values in (448, 512) become ±448.  A
-    block without a finite nonzero value gets byte 127; NaN → ``0x7F`` without
-    a say in the scale; ±inf → ±448.  ``0xFF`` (E8M0 NaN) is never produced.
-    ``x`` is taken as float32 (float64 is kept for the scale and the scaling,
-    the element rounding then goes through float32)."""
-    x = np.asarray(x)
-    x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
-    K = x.shape[-1]
-    if block <= 0 or K % block:
-        raise ValueError(f"the last axis ({K}) must be a multiple of the block ({block})")
-    xb = x.reshape(x.shape[:-1] + (K // block, block)).astype(np.float64)
-    amax = np.where(np.isfinite(xb), np.abs(xb), 0.0).max(axis=-1)
-    _, ex = np.frexp(amax)  # amax = m · 2^ex, 0.5 <= m < 1: floor(log2 amax) = ex − 1
-    e = np.clip(np.where(amax > 0, ex.astype(np.int64) - 9, 0), -127, 127)
-    with np.errstate(over="ignore", invalid="ignore"):
-        scaled = np.ldexp(xb, -e[..., None]).astype(np.float32)
-    return to_fp8_e4m3_bits(scaled).reshape(x.shape), (e + 127).astype(np.uint8)
-
-
-def from_mxfp8(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
-    """MXFP8 → float32: ``e4m3(code) · 2^(scale − 127)`` with one scale per
-    ``K / scales.shape[-1]`` elements of the last axis.  (The product is taken
-    in float64; what float32 cannot hold rounds, overflows or underflows.)"""
-    codes, scales = np.asarray(codes, np.uint8), np.asarray(scales, np.uint8)
-    nb = scales.shape[-1]
-    v = from_fp8_e4m3_bits(codes).astype(np.float64).reshape(scales.shape + (codes.shape[-1] // nb,))
-    with np.errstate(over="ignore", invalid="ignore"):
-        return (v * e8m0_to_f64(scales)[..., None]).astype(np.float32).reshape(codes.shape)
-
-
-def pack_mx_scales(s: np.ndarray) -> np.ndarray:
-    """Row-major scale bytes ``[R][K/32]`` → the kernels' packed dwords
-    (kernels/sgemm_mxfp8.hip): uint32 ``[K/128][R/64][64]``, byte ``i`` of
-    dword ``(kt·R/64 + g)·64 + l`` = ``s[g·64 + i·16 + l % 16][kt·4 + l // 16]``.
-    R % 64 = 0 and (K/32) % 4 = 0."""
-    s = np.asarray(s, np.uint8)
-    R, nb = s.shape
-    if R % 64 or nb % 4:
-        raise ValueError(f"rows % 64 and blocks % 4 must be 0 (got {R}, {nb})")
-    x = s.reshape(R // 64, 4, 16, nb // 4, 4)  # g i fr kt fq
-    return np.ascontiguousarray(x.transpose(3, 0, 4, 2, 1)).view("<u4").reshape(nb // 4, R // 64, 64)  # kt g fq fr [i]
-
-
-def unpack_mx_scales(p: np.ndarray) -> np.ndarray:
-    """Inverse of :func:`pack_mx_scales`: uint32 ``[K/128][R/64][64]`` → uint8 ``[R][K/32]``."""
-    p = np.ascontiguousarray(p, dtype="<u4")
-    KT, G, _ = p.shape
-    x = p.view(np.uint8).reshape(KT, G, 4, 16, 4)  # kt g fq fr i
-    return np.ascontiguousarray(x.transpose(1, 4, 3, 0, 2)).reshape(G * 64, KT * 4)  # g i fr kt fq
-
-
-# OCP e2m1 (MXFP4's element): code s e e m
-_FP4_E2M1 = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0,
-                      -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0], np.float32)
-# the midpoints between neighbouring magnitudes; a value on midpoint i lies
-# between codes i and i + 1 and goes to the even one
-_FP4_MIDPOINTS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)
-FP4_E2M1_EMAX = 2  # exponent of e2m1's largest binade (4, 6)
-
-
-def to_fp4_e2m1_codes(x: np.ndarray) -> np.ndarray:
-    """fp32 (or fp64) → OCP e2m1 codes 0..15, one per element, as uint8: bit
-    layout ``s e e m``, codes 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6 and 8..15 their
-    negatives (−0 kept).  Round to nearest even (a value halfway between two
-    neighbours goes to the one whose mantissa bit is 0); finite values beyond
-    ±6 and ±inf SATURATE to ±6.  e2m1 has no NaN: a NaN gives code 0."""
-    x = np.asarray(x)
-    x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
-    a = np.abs(x)
-    code = np.zeros(x.shape, np.uint8)
-    with np.errstate(invalid="ignore"):
-        for i, mid in enumerate(_FP4_MIDPOINTS):
-            code += (a >= mid) if i % 2 else (a > mid)
-    nan = np.isnan(x)
-    return np.where(nan, np.uint8(0), code | (np.signbit(x).astype(np.uint8) << 3)).astype(np.uint8)
-
-
-def from_fp4_e2m1_codes(c: np.ndarray) -> np.ndarray:
-    """OCP e2m1 codes (uint8, 0..15, one per element) → fp32, by table."""
-    c = np.asarray(c, dtype=np.uint8)
-    if c.size and int(c.max()) > 15:
-        raise ValueError("e2m1 codes are 0..15")
-    return _FP4_E2M1[c]
-
-
-def pack_fp4(codes: np.ndarray) -> np.ndarray:
-    """e2m1 codes ``[..., K]`` (0..15) → packed bytes ``[..., K/2]``: element
-    ``2i`` in bits 0–3 of byte ``i``, element ``2i + 1`` in bits 4–7 (the
-    public layout of every fp4x2 array)."""
-    c = np.asarray(codes, dtype=np.uint8)
-    if c.shape[-1] % 2:
-        raise ValueError(f"the last axis ({c.shape[-1]}) must be even")
-    if c.size and int(c.max()) > 15:
-        raise ValueError("e2m1 codes are 0..15")
-    return (c[..., 0::2] | (c[..., 1::2] << 4)).astype(np.uint8)
-
-
-def unpack_fp4(packed: np.ndarray) -> np.ndarray:
-    """Inverse of :func:`pack_fp4`: bytes ``[..., K/2]`` → codes ``[..., K]``."""
-    p = np.asarray(packed, dtype=np.uint8)
-    return np.stack((p & 15, p >> 4), axis=-1).reshape(p.shape[:-1] + (2 * p.shape[-1],))
-
-
-def to_mxfp4(x: np.ndarray, block: int = MX_BLOCK):
-    """OCP Microscaling (MX v1.0) MXFP4 along the last axis: ``(packed uint8
-    [..., K/2], scales uint8 [..., K/block])``, the elements packed as
-    :func:`pack_fp4` does.  Per block the shared exponent is ``e = floor(log2(max
-    |x| over the block's finite values)) − 2`` (2: the exponent of e2m1's
-    largest binade), clamped to [−127, 127], the scale byte ``e + 127`` and the
-    elements ``to_fp4_e2m1_codes(x · 2^−e)``: round to nearest even,
-    saturating, so scaled values in (6, 8) become ±6.  A block without a
-    finite nonzero value gets byte 127; ±inf → ±6 without a say in the scale.
-
-    NaN: e2m1 has no NaN code, so a NaN cannot stay in its element.  A block
-    that contains a NaN gets the scale byte ``0xFF`` (E8M0 NaN), which makes
-    the WHOLE block NaN in OCP MX (:func:`from_mxfp4`, the kernels); its NaN
-    elements get code 0 and its other elements the codes they would have had.
-    (:func:`to_mxfp8` never produces ``0xFF``: e4m3 has a NaN of its own.)
-
-    The scaling and the element rounding are done in float64, where both are
-    exact for float32 and float64 input alike."""
-    x = np.asarray(x)
-    x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
-    K = x.shape[-1]
-    if block <= 0 or block % 2 or K % block:
-        raise ValueError(f"the last axis ({K}) must be a multiple of the block ({block}), the block even")
-    xb = x.reshape(x.shape[:-1] + (K // block, block)).astype(np.float64)
-    amax = np.where(np.isfinite(xb), np.abs(xb), 0.0).max(axis=-1)
-    _, ex = np.frexp(amax)  # amax = m · 2^ex, 0.5 <= m < 1: floor(log2 amax) = ex − 1
-    e = np.clip(np.where(amax > 0, ex.astype(np.int64) - 1 - FP4_E2M1_EMAX, 0), -127, 127)
-    with np.errstate(over="ignore", invalid="ignore"):
-        codes = to_fp4_e2m1_codes(np.ldexp(xb, -e[..., None]))
-    scales = np.where(np.isnan(xb).any(axis=-1), 0xFF, e + 127).astype(np.uint8)
-    return pack_fp4(codes.reshape(x.shape)), scales
-
-
-def from_mxfp4(packed: np.ndarray, scales: np.ndarray) -> np.ndarray:
-    """MXFP4 → float32: ``e2m1(code) · 2^(scale − 127)`` with one scale per
-    ``K / scales.shape[-1]`` elements of the last axis, K twice the packed
-    length; a scale byte ``0xFF`` makes its whole block NaN.  (The product is
-    taken in float64; what float32 cannot hold rounds, overflows or underflows.)"""
-    packed, scales = np.asarray(packed, np.uint8), np.asarray(scales, np.uint8)
-    nb = scales.shape[-1]
-    v = from_fp4_e2m1_codes(unpack_fp4(packed)).astype(np.float64)
-    shape = v.shape
-    v = v.reshape(scales.shape + (shape[-1] // nb,))
-    with np.errstate(over="ignore", invalid="ignore"):
-        return (v * e8m0_to_f64(scales)[..., None]).astype(np.float32).reshape(shape)
-
-
 def decode_operand(arr: ClArray) -> np.ndarray:
     """The host array of a GEMM operand as numbers: bf16, fp8 and fp4x2 arrays
     hold bit patterns (``is_fp8``; ``is_fp4``: two e2m1 codes per byte, so the
@@ -408,74 +183,35 @@ def decode_operand(arr: ClArray) -> np.ndarray:
     return from_bf16_bits(x) if getattr(arr, "is_bf16", False) or x.dtype == np.uint16 else x
 
 
-def tile_coords(t: np.ndarray, M: int, N: int, BM: int, BN: int, group_m: int, panels: int = 0):
-    """Tile index → (tile row, tile col) under the kernel's order
-    (``cek_tile_coords`` in kernels/cek_kernel.h): grouped rows, or square
-    shells of ``panels`` row panels (shell s = R_s then C_s)."""
-    t = np.asarray(t)
-    ntm, ntn = M // BM, N // BN
-
-    def grouped(r, rows, cols):
-        gm = max(1, group_m)
-        per = gm * cols
-        first = (r // per) * gm
-        gsz = np.minimum(rows - first, gm)
-        in_g = r % per
-        return first + in_g % gsz, in_g // gsz
-
-    if panels <= 0:
-        return grouped(t, ntm, ntn)
-    pm, pn = ntm // panels, ntn // panels
-    tm = np.empty_like(t)
-    tn = np.empty_like(t)
-    s = np.floor(np.sqrt(t // (pm * pn))).astype(np.int64)
-    s = np.where((s + 1) ** 2 * pm * pn <= t, s + 1, s)
-    s = np.where(s * s * pm * pn > t, s - 1, s)
-    r = t - s * s * pm * pn
-    r_tiles = pm * (s + 1) * pn
-    for sh in np.unique(s):
-        sel = s == sh
-        rr = r[sel]
-        isr = rr < r_tiles[sel]
-        a, b = grouped(rr[isr], pm, (sh + 1) * pn)
-        c, d = grouped(rr[~isr] - pm * (sh + 1) * pn, max(sh * pm, 1), pn)
-        out_m = np.empty(rr.shape, t.dtype)
-        out_n = np.empty(rr.shape, t.dtype)
-        out_m[isr], out_n[isr] = a + sh * pm, b
-        out_m[~isr], out_n[~isr] = c, d + sh * pn
-        tm[sel], tn[sel] = out_m, out_n
-    return tm, tn
-
-
-def untile(c: np.ndarray, M: int, N: int, BM: int, BN: int, group_m: int = 1, geom=None,
-           panels: int = 0) -> np.ndarray:
-    """Tile-major C (the kernel's tile order) → row-major [M][N]; ``geom``:
-    the tile's wave geometry when its elements are in fragment order (bf16
-    kernels), None for row-major tiles; ``panels``: shell order."""
-    ntm, ntn = M // BM, N // BN
-    tiles = c.reshape(ntm * ntn, BM, BN) if geom is None else tile_to_rows(c.reshape(ntm * ntn, BM * BN), geom)
-    tm, tn = tile_coords(np.arange(ntm * ntn), M, N, BM, BN, group_m, panels)
-    out = np.empty((ntm, ntn, BM, BN), c.dtype)
-    out[tm, tn] = tiles
-    return out.transpose(0, 2, 1, 3).reshape(M, N)
-
-
 class GemmBf16:
+    # What a format states; the constructor below does the rest for all five.
+    TILE_TABLE = TILES
+    TILE_GEOM = TILE_WAVES  # tile -> wave geometry (C tiles in fragment order); None: C tiles row-major
+    K_MULTIPLE = 64
+    POSITIVE_DIMS = False  # the 8-bit and 4-bit classes also refuse M, N, K <= 0
+    LIBS = GEMM_LIBS
+    OPERAND_DTYPE = "bfloat16"
+    PER_ITEM = 1  # elements per storage item of A / B
+    _encode = staticmethod(to_bf16_bits)  # fp32 values -> what A / B store
+
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
                  group_m: int = 4, split_k: int = 1, wave_granularity: bool | None = None,
                  exchange_shift: int | None = None, handover_spin_limit: int = 0):
-        BM, BN, L, kname = TILES[tile]
+        BM, BN, L, kname = self.TILE_TABLE[tile]
         self.tile = tile
-        if M % BM or N % BN or K % 64:
-            raise ValueError(f"M%{BM}, N%{BN} and K%64 must be 0 (got {M},{N},{K})")
+        if M % BM or N % BN or K % self.K_MULTIPLE or (self.POSITIVE_DIMS and min(M, N, K) <= 0):
+            raise ValueError(f"M%{BM}, N%{BN} and K%{self.K_MULTIPLE} must be 0"
+                             + (" and M, N, K positive" if self.POSITIVE_DIMS else "") + f" (got {M},{N},{K})")
+        # split-K, exchange and row-major C are variants of the bf16 tiles alone
+        bf16 = self.TILE_TABLE is TILES
         if split_k > 1:
             if tile not in SPLIT_K_TILES:
                 raise ValueError(f"split-K is available for tiles {sorted(SPLIT_K_TILES)}")
             if (K // 64) % split_k:
                 raise ValueError(f"K/64 ({K // 64}) must be divisible by split_k ({split_k})")
             kname = kname + "_sk"
-        self.exchange = tile in EXCHANGE_TILES
+        self.exchange = bf16 and tile in EXCHANGE_TILES
         shift = 0
         if self.exchange:
             if (K // 64) % 2:
@@ -486,12 +222,12 @@ class GemmBf16:
                 shift = max(0, min(shift, K // 128 - 1))  # the helper keeps >= 1 K-tile
         self.exchange_shift = shift
         self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
-        self.geom = TILE_WAVES[tile]  # C tiles in fragment order
-        self.row_major_c = tile in ROW_MAJOR_TILES
+        self.geom = self.TILE_GEOM[tile] if self.TILE_GEOM else None
+        self.row_major_c = bf16 and tile in ROW_MAJOR_TILES
         self.split_k = max(1, int(split_k))
         self.tiles = (M // BM) * (N // BN)
         self.global_range = self.tiles * self.split_k * L
-        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library(*GEMM_LIBS))
+        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library(*self.LIBS))
         self.group_m = group_m
         # dims[7]: the owner's wait for the helper's partial, in polls (0: the
         # kernel default, 65536; -1: the owner claims at once and the helper
@@ -499,10 +235,11 @@ class GemmBf16:
         # the helper claims the hand-back at once — forced fall-backs)
         self.dims = ClArray(np.array([M, N, K, group_m, self.split_k, shift, 0, int(handover_spin_limit)], np.int32))
         self.dims.write = False
-        self.A = ClArray(M * K, "bfloat16")
-        self.B = ClArray(N * K, "bfloat16")
+        self.A = ClArray(M * K // self.PER_ITEM, self.OPERAND_DTYPE)
+        self.B = ClArray(N * K // self.PER_ITEM, self.OPERAND_DTYPE)
+        scales = self._alloc_scales()
         self.C = ClArray(M * N, np.float32)
-        for a in (self.A, self.B):
+        for a in (self.A, self.B, *scales):
             a.write = False
         self.C.read = False
         self.C.elements_per_work_item = BM * BN // (L * self.split_k)
@@ -520,12 +257,20 @@ class GemmBf16:
             self.counters.write = False
             self.extra = [self.W, self.counters]
         if fill == "random":
-            rng = np.random.default_rng(seed)
-            self.A.array[:] = to_bf16_bits(rng.uniform(-1, 1, M * K).astype(np.float32))
-            self.B.array[:] = to_bf16_bits(rng.uniform(-1, 1, N * K).astype(np.float32))
+            self._fill_random(np.random.default_rng(seed))
         self._uploaded = False
         self.wave_granularity = wave_granularity
         self._orders = {}  # compute id -> shell panels of its tile order (0: grouped)
+
+    def _alloc_scales(self) -> tuple:
+        """Allocate what a format keeps beside ``A`` and ``B`` (the MX formats:
+        their scale arrays); returns those of them the kernels only read."""
+        return ()
+
+    def _fill_random(self, rng) -> None:
+        """Uniform [−1, 1) values in the operands' format, A then B."""
+        self.A.array[:] = self._encode(rng.uniform(-1, 1, self.M * self.K).astype(np.float32))
+        self.B.array[:] = self._encode(rng.uniform(-1, 1, self.N * self.K).astype(np.float32))
 
     def granularity(self) -> int:
         """Balancer unit in work items.  One tile (all its K-splits) by
@@ -559,7 +304,7 @@ class GemmBf16:
     def _row_items(self) -> int:
         """Storage items of one operand row in ``A`` / ``B``: K, one per
         element (GemmMxFp4: K/2 bytes of two elements each)."""
-        return self.K
+        return self.K // self.PER_ITEM
 
     def _group_work_items(self) -> int:
         """Work items of one tile group (``group_m`` tile rows × every tile
@@ -640,7 +385,8 @@ class GemmBf16:
             p = torch.from_numpy(x).to(device)
             codes = torch.stack((p & 15, p >> 4), dim=-1).reshape(rows, self.K).long()
             del p
-            return torch.from_numpy(_FP4_E2M1.astype(np.float64)).to(device)[codes]
+            table = from_fp4_e2m1_codes(np.arange(16, dtype=np.uint8)).astype(np.float64)
+            return torch.from_numpy(table).to(device)[codes]
         if getattr(arr, "is_fp8", False):
             # e4m3fn bit patterns, decoded on the host (every e4m3 value is exact in bf16)
             t = torch.from_numpy(x).view(torch.float8_e4m3fn).to(torch.bfloat16).to(device)
@@ -789,7 +535,7 @@ class GemmBf16:
                 g = self.cr._cores.global_base + dev
                 lo, n = refs[g] * e, rng[g] * e
                 self._download_slice(dev, lo, n)
-        if getattr(self, "row_major_c", False):
+        if self.row_major_c:
             return self.C.array.reshape(self.M, self.N).copy()
         return untile(self.C.array, self.M, self.N, self.BM, self.BN, self.group_m, self.geom,
                       self._orders.get(self.cr._cores.last_compute_id, 0))
@@ -845,7 +591,7 @@ class GemmBf16:
             tm, tn = tile_coords(picks, self.M, self.N, self.BM, self.BN, self.group_m,
                                  self._orders.get(compute_id, 0))
             for t, r, c in zip(picks, tm, tn):
-                if getattr(self, "row_major_c", False):
+                if self.row_major_c:
                     got = self.C.array.reshape(self.M, self.N)[r * self.BM:(r + 1) * self.BM,
                                                                c * self.BN:(c + 1) * self.BN].astype(np.float64)
                 else:
@@ -892,7 +638,7 @@ class GemmBf16:
                 tm_t = torch.from_numpy(np.asarray(tm, np.int64)).to(device)
                 tn_t = torch.from_numpy(np.asarray(tn, np.int64)).to(device)
                 c = torch.from_numpy(self.C.array).to(device)
-                if getattr(self, "row_major_c", False):
+                if self.row_major_c:
                     got = c.view(ntm, BM, ntn, BN).permute(0, 2, 1, 3)[tm_t, tn_t]
                 else:
                     flat = c.view(-1, BM * BN)[t0:t0 + nt]
@@ -932,44 +678,17 @@ class GemmF32(GemmBf16):
     (same grouped tile order, so the same range partitioning and
     wave-quantized balancing apply)."""
 
+    TILE_TABLE = F32_TILES
+    TILE_GEOM = None  # the fp32 kernels store C tiles row-major
+    K_MULTIPLE = 32
+    LIBS = ("sgemm_f32",)
+    OPERAND_DTYPE = np.float32
+    _encode = staticmethod(lambda x: x)
+
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256g8i",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
                  group_m: int = 4, wave_granularity: bool | None = None):
-        BM, BN, L, kname = F32_TILES[tile]
-        self.tile = tile
-        if M % BM or N % BN or K % 32:
-            raise ValueError(f"M%{BM}, N%{BN} and K%32 must be 0 (got {M},{N},{K})")
-        self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
-        self.geom = None  # the fp32 kernels store C tiles row-major
-        self.row_major_c = False
-        self.exchange = False
-        self.split_k = 1
-        self.tiles = (M // BM) * (N // BN)
-        self.global_range = self.tiles * L
-        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_f32"))
-        self.group_m = group_m
-        self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
-        self.dims.write = False
-        self.A = ClArray(M * K, np.float32)
-        self.B = ClArray(N * K, np.float32)
-        self.C = ClArray(M * N, np.float32)
-        for a in (self.A, self.B):
-            a.write = False
-        self.C.read = False
-        self.C.elements_per_work_item = BM * BN // L
-        self.extra = []
-        if fill == "random":
-            rng = np.random.default_rng(seed)
-            self.A.array[:] = rng.uniform(-1, 1, M * K).astype(np.float32)
-            self.B.array[:] = rng.uniform(-1, 1, N * K).astype(np.float32)
-        self._uploaded = False
-        self.wave_granularity = wave_granularity
-        self._orders = {}
-
-    def reference(self, rows: slice = slice(None)) -> np.ndarray:
-        a = self.A.array.reshape(self.M, self.K)[rows].astype(np.float64)
-        b = self.B.array.reshape(self.N, self.K).astype(np.float64)
-        return a @ b.T
+        super().__init__(M, N, K, devices, tile, cruncher, fill, seed, group_m, wave_granularity=wave_granularity)
 
 
 class GemmFp8(GemmBf16):
@@ -989,40 +708,18 @@ class GemmFp8(GemmBf16):
     a neighbour is dropped.  Data of a narrow range inside every such group
     (small integers, uniform random values) is summed as fp32 would."""
 
+    TILE_TABLE = FP8_TILES
+    TILE_GEOM = FP8_TILE_WAVES
+    K_MULTIPLE = 128
+    POSITIVE_DIMS = True
+    LIBS = ("sgemm_fp8",)
+    OPERAND_DTYPE = "float8_e4m3fn"
+    _encode = staticmethod(to_fp8_e4m3_bits)
+
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
                  group_m: int = 4, wave_granularity: bool | None = None):
-        BM, BN, L, kname = FP8_TILES[tile]
-        self.tile = tile
-        if M % BM or N % BN or K % 128 or min(M, N, K) <= 0:
-            raise ValueError(f"M%{BM}, N%{BN} and K%128 must be 0 and M, N, K positive (got {M},{N},{K})")
-        self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
-        self.geom = FP8_TILE_WAVES[tile]  # C tiles in fragment order
-        self.row_major_c = False
-        self.exchange = False
-        self.exchange_shift = 0
-        self.split_k = 1
-        self.tiles = (M // BM) * (N // BN)
-        self.global_range = self.tiles * L
-        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_fp8"))
-        self.group_m = group_m
-        self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
-        self.dims.write = False
-        self.A = ClArray(M * K, "float8_e4m3fn")
-        self.B = ClArray(N * K, "float8_e4m3fn")
-        self.C = ClArray(M * N, np.float32)
-        for a in (self.A, self.B):
-            a.write = False
-        self.C.read = False
-        self.C.elements_per_work_item = BM * BN // L
-        self.extra = []
-        if fill == "random":
-            rng = np.random.default_rng(seed)
-            self.A.array[:] = to_fp8_e4m3_bits(rng.uniform(-1, 1, M * K).astype(np.float32))
-            self.B.array[:] = to_fp8_e4m3_bits(rng.uniform(-1, 1, N * K).astype(np.float32))
-        self._uploaded = False
-        self.wave_granularity = wave_granularity
-        self._orders = {}
+        super().__init__(M, N, K, devices, tile, cruncher, fill, seed, group_m, wave_granularity=wave_granularity)
 
 
 class GemmMxFp8(GemmBf16):
@@ -1059,51 +756,40 @@ class GemmMxFp8(GemmBf16):
     until :meth:`sync_operands`, which every host reference (``verify*``,
     ``reference``) calls first."""
 
+    TILE_TABLE = MXFP8_TILES
+    TILE_GEOM = MXFP8_TILE_WAVES
+    K_MULTIPLE = 128
+    POSITIVE_DIMS = True
+    LIBS = ("sgemm_mxfp8", "mx_quantize")
+    OPERAND_DTYPE = "float8_e4m3fn"
+    _to_mx = staticmethod(to_mxfp8)  # [rows][K] fp32 values -> (what A / B store, scale bytes)
+
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
                  group_m: int = 4, wave_granularity: bool | None = None):
-        BM, BN, L, kname = MXFP8_TILES[tile]
-        self.tile = tile
-        if M % BM or N % BN or K % 128 or min(M, N, K) <= 0:
-            raise ValueError(f"M%{BM}, N%{BN} and K%128 must be 0 and M, N, K positive (got {M},{N},{K})")
-        self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
-        self.geom = MXFP8_TILE_WAVES[tile]  # C tiles in fragment order
-        self.row_major_c = False
-        self.exchange = False
-        self.exchange_shift = 0
-        self.split_k = 1
-        self.tiles = (M // BM) * (N // BN)
-        self.global_range = self.tiles * L
-        self.cr = cruncher or ClNumberCruncher(devices, "", prebuilt=library("sgemm_mxfp8", "mx_quantize"))
         self._stale = set()  # operands quantised on the device whose host arrays are behind
         self._quantizers = {}
-        self.group_m = group_m
-        self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
-        self.dims.write = False
-        self.A = ClArray(M * K, "float8_e4m3fn")
-        self.B = ClArray(N * K, "float8_e4m3fn")
+        super().__init__(M, N, K, devices, tile, cruncher, fill, seed, group_m, wave_granularity=wave_granularity)
+
+    def _alloc_scales(self) -> tuple:
+        M, N, K = self.M, self.N, self.K
         self.SA = ClArray(np.full(M * K // MX_BLOCK, 127, np.uint8))  # 2^0
         self.SB = ClArray(np.full(N * K // MX_BLOCK, 127, np.uint8))
         # the packed scales the kernels read; run() fills them from SA / SB
         self._SAp = ClArray(np.zeros(M * K // 128, np.uint32))
         self._SBp = ClArray(np.zeros(N * K // 128, np.uint32))
-        self.C = ClArray(M * N, np.float32)
-        for a in (self.A, self.B, self._SAp, self._SBp):
-            a.write = False
-        self.C.read = False
-        self.C.elements_per_work_item = BM * BN // L
-        self.extra = []
-        if fill == "random":
-            rng = np.random.default_rng(seed)
-            for arr, sc, rows in ((self.A, self.SA, M), (self.B, self.SB, N)):
-                x = rng.uniform(-1, 1, (rows, K // MX_BLOCK, MX_BLOCK))
-                x = np.ldexp(x, rng.integers(-12, 13, (rows, K // MX_BLOCK, 1)))
-                codes, scales = to_mxfp8(x.astype(np.float32).reshape(rows, K))
-                arr.array[:] = codes.ravel()
-                sc.array[:] = scales.ravel()
-        self._uploaded = False
-        self.wave_granularity = wave_granularity
-        self._orders = {}
+        return self._SAp, self._SBp
+
+    def _fill_random(self, rng) -> None:
+        """Per operand, A then B: uniform [−1, 1) values times ``2^u`` per
+        block, u an integer uniform in [−12, 12], quantised by the format."""
+        K = self.K
+        for arr, sc, rows in ((self.A, self.SA, self.M), (self.B, self.SB, self.N)):
+            x = rng.uniform(-1, 1, (rows, K // MX_BLOCK, MX_BLOCK))
+            x = np.ldexp(x, rng.integers(-12, 13, (rows, K // MX_BLOCK, 1)))
+            codes, scales = self._to_mx(x.astype(np.float32).reshape(rows, K))
+            arr.array[:] = codes.ravel()
+            sc.array[:] = scales.ravel()
 
     def _inputs(self, upload: bool) -> tuple:
         # an operand quantised on the device is resident with its packed
@@ -1147,16 +833,12 @@ class GemmMxFp8(GemmBf16):
         e.g. another kernel of this cruncher wrote it).  ``download=True``
         also brings the codes and scales into ``A`` / ``SA`` (``B`` / ``SB``);
         otherwise the host arrays are stale until :meth:`sync_operands`."""
-        from .quantize import MxFp8Quantizer
-
         self._quantize_with(MxFp8Quantizer, 0x4D58, name, x, src, download)
 
     def _quantize_with(self, quantizer, base_id: int, name: str, x, src, download: bool) -> None:
         """:meth:`quantize` with the quantizer class of the format; the
         operand's quantise and pack computes run under ``base_id`` (A) or
         ``base_id + 2`` (B) and the id after it."""
-        from .quantize import _src_name
-
         if name not in ("A", "B"):
             raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
         rows = self.M if name == "A" else self.N
@@ -1228,7 +910,8 @@ class GemmMxFp8(GemmBf16):
         return (x.view(-1, self.K // MX_BLOCK, MX_BLOCK) * sc[..., None]).view(-1, self.K)
 
     def _no_shells(self, *a, **k):
-        raise NotImplementedError("GemmMxFp8 has no shell paths: the shell streamer (csrc/shell_gemm.cpp) passes no scales")
+        raise NotImplementedError(f"{type(self).__name__} has no shell paths: the shell streamer "
+                                  "(csrc/shell_gemm.cpp) passes no scales")
 
     run_shells = run_host_shells = verify_shells = verify_shells_full = _no_shells
 
@@ -1264,55 +947,13 @@ class GemmMxFp4(GemmMxFp8):
     (OCP MX) and with it the row or column of C.  profiles/gemm_mxfp4.md has
     what the single-instruction probe measured."""
 
-    def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
-                 cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
-                 group_m: int = 4, wave_granularity: bool | None = None):
-        BM, BN, L, kname = MXFP4_TILES[tile]
-        self.tile = tile
-        if M % BM or N % BN or K % 256 or min(M, N, K) <= 0:
-            raise ValueError(f"M%{BM}, N%{BN} and K%256 must be 0 and M, N, K positive (got {M},{N},{K})")
-        self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
-        self.geom = MXFP4_TILE_WAVES[tile]  # C tiles in fragment order
-        self.row_major_c = False
-        self.exchange = False
-        self.exchange_shift = 0
-        self.split_k = 1
-        self.tiles = (M // BM) * (N // BN)
-        self.global_range = self.tiles * L
-        self.cr = cruncher or ClNumberCruncher(devices, "",
-                                               prebuilt=library("sgemm_mxfp4", "mx4_quantize", "mx_quantize"))
-        self._stale = set()  # operands quantised on the device whose host arrays are behind
-        self._quantizers = {}
-        self.group_m = group_m
-        self.dims = ClArray(np.array([M, N, K, group_m, 1, 0, 0, 0], np.int32))
-        self.dims.write = False
-        self.A = ClArray(M * K // 2, "float4_e2m1fn_x2")
-        self.B = ClArray(N * K // 2, "float4_e2m1fn_x2")
-        self.SA = ClArray(np.full(M * K // MX_BLOCK, 127, np.uint8))  # 2^0
-        self.SB = ClArray(np.full(N * K // MX_BLOCK, 127, np.uint8))
-        # the packed scales the kernels read; run() fills them from SA / SB
-        self._SAp = ClArray(np.zeros(M * K // 128, np.uint32))
-        self._SBp = ClArray(np.zeros(N * K // 128, np.uint32))
-        self.C = ClArray(M * N, np.float32)
-        for a in (self.A, self.B, self._SAp, self._SBp):
-            a.write = False
-        self.C.read = False
-        self.C.elements_per_work_item = BM * BN // L
-        self.extra = []
-        if fill == "random":
-            rng = np.random.default_rng(seed)
-            for arr, sc, rows in ((self.A, self.SA, M), (self.B, self.SB, N)):
-                x = rng.uniform(-1, 1, (rows, K // MX_BLOCK, MX_BLOCK))
-                x = np.ldexp(x, rng.integers(-12, 13, (rows, K // MX_BLOCK, 1)))
-                packed, scales = to_mxfp4(x.astype(np.float32).reshape(rows, K))
-                arr.array[:] = packed.ravel()
-                sc.array[:] = scales.ravel()
-        self._uploaded = False
-        self.wave_granularity = wave_granularity
-        self._orders = {}
-
-    def _row_items(self) -> int:
-        return self.K // 2  # bytes: two elements each
+    TILE_TABLE = MXFP4_TILES
+    TILE_GEOM = MXFP4_TILE_WAVES
+    K_MULTIPLE = 256
+    LIBS = ("sgemm_mxfp4", "mx4_quantize", "mx_quantize")
+    OPERAND_DTYPE = "float4_e2m1fn_x2"
+    PER_ITEM = 2  # bytes of two elements each
+    _to_mx = staticmethod(to_mxfp4)
 
     def quantize(self, *a, **k):
         raise NotImplementedError("GemmMxFp4 takes operands quantised on the host (to_mxfp4): on-device MXFP4 "
@@ -1328,12 +969,4 @@ class GemmMxFp4(GemmMxFp8):
         byte ``0xFF``).  The packed codes, the row-major scales and the packed
         scales stay resident for the next resident :meth:`run`; the host
         arrays are stale until :meth:`sync_operands` unless ``download``."""
-        from .quantize import MxFp4Quantizer
-
         self._quantize_with(MxFp4Quantizer, 0x4D60, name, x, src, download)
-
-    def _no_shells(self, *a, **k):
-        raise NotImplementedError("GemmMxFp4 has no shell paths: the shell streamer (csrc/shell_gemm.cpp) passes no "
-                                  "scales")
-
-    run_shells = run_host_shells = verify_shells = verify_shells_full = _no_shells

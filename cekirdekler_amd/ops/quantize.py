@@ -1,7 +1,7 @@
 """MXFP8 quantisation on the device (``kernels/mx_quantize.hip``): fp32 or
 bf16 in device memory in, OCP e4m3fn codes plus one E8M0 scale byte per block
 of 32 out, and the scales once more in the packed layout the MXFP8 GEMM
-kernels read.  The result is :func:`cekirdekler_amd.ops.gemm.to_mxfp8`'s bit
+kernels read.  The result is :func:`cekirdekler_amd.ops.codecs.to_mxfp8`'s bit
 for bit (:func:`mxfp8_reference`); :func:`mxfp8_kernel_model` is the kernels'
 algorithm in integer and float32 numpy operations, the executable
 specification the host tests hold against the float64 codec.
@@ -17,7 +17,7 @@ dword) builds it from the whole row-major scales.
 
 MXFP4 (``kernels/mx4_quantize.hip``, :class:`MxFp4Quantizer`,
 :func:`mxfp4_reference`, :func:`mxfp4_kernel_model`) is the same machinery
-with e2m1 codes, two per byte, and :func:`cekirdekler_amd.ops.gemm.to_mxfp4`
+with e2m1 codes, two per byte, and :func:`cekirdekler_amd.ops.codecs.to_mxfp4`
 as the codec; its scales go through the same pack kernel.
 """
 from __future__ import annotations
@@ -26,7 +26,7 @@ import numpy as np
 
 from ..arrays import ClArray
 from ..cruncher import ClComputeError, ClNumberCruncher
-from .gemm import MX_BLOCK, from_bf16_bits, pack_fp4, to_mxfp4, to_mxfp8
+from .codecs import FP4_E2M1_EMAX, FP8_E4M3_EMAX, MX_BLOCK, from_bf16_bits, pack_fp4, to_mxfp4, to_mxfp8
 from .library import LIBRARY, library
 
 QUANTIZE_KERNELS = {"float32": "cek_mx_quantize_f32", "bfloat16": "cek_mx_quantize_bf16"}
@@ -43,14 +43,20 @@ def _src_name(src) -> str:
     return key
 
 
+def _reference(codec, x) -> tuple:
+    """``codec`` of the float32 input, or of the decoded values of bf16 bit
+    patterns (a uint16 array or a bf16 :class:`ClArray`)."""
+    if isinstance(x, ClArray):
+        x = x.array
+    x = np.asarray(x)
+    return codec(from_bf16_bits(x) if x.dtype == np.uint16 else x.astype(np.float32, copy=False))
+
+
 def mxfp8_reference(x) -> tuple:
     """What the quantise kernels compute: :func:`to_mxfp8` of the float32
     input, or of the decoded values of bf16 bit patterns (a uint16 array or a
     bf16 :class:`ClArray`): ``(codes, scales)``, blocks along the last axis."""
-    if isinstance(x, ClArray):
-        x = x.array
-    x = np.asarray(x)
-    return to_mxfp8(from_bf16_bits(x) if x.dtype == np.uint16 else x.astype(np.float32, copy=False))
+    return _reference(to_mxfp8, x)
 
 
 def e4m3_convert_model(y: np.ndarray) -> np.ndarray:
@@ -68,10 +74,13 @@ def e4m3_convert_model(y: np.ndarray) -> np.ndarray:
     return np.where(c < np.uint32(0x3C800000), sub, norm) | s
 
 
-def _model_blocks(x, src: str) -> tuple:
+def _model_blocks(x, src: str, emax: int) -> tuple:
     """The kernel models' common start: ``x`` as uint32 bit patterns in blocks
     of 32 (``[blocks][32]``), their keys ``|x| bits + 2^23`` as int32, and per
-    block the bits of the finite |x| maximum (0 where nothing is finite)."""
+    block the scale byte ``max(E − emax, 0)`` from the exponent field E of the
+    finite |x| maximum (127 when that is zero or nothing is finite; ``emax``:
+    the exponent of the element format's largest binade) and the float32
+    multiplier ``2^-e``, bits ``(254 − byte) << 23``."""
     src = _src_name(src)
     x = np.asarray(x)
     if src == "bfloat16":
@@ -85,7 +94,10 @@ def _model_blocks(x, src: str) -> tuple:
     ub = np.ascontiguousarray(u).reshape(-1, MX_BLOCK)
     key = ((ub & np.uint32(0x7FFFFFFF)) + np.uint32(0x00800000)).view(np.int32)
     amax = (np.maximum(key.max(axis=1), np.int32(0x00800000)) - np.int32(0x00800000)).astype(np.uint32)
-    return x, ub, key, amax
+    field = (amax >> np.uint32(23)).astype(np.int32)
+    sb = np.where(amax == 0, 127, np.maximum(field - emax, 0)).astype(np.uint32)
+    mult = ((np.uint32(254) - sb) << np.uint32(23)).view(np.float32)
+    return x, ub, key, sb, mult
 
 
 def mxfp8_kernel_model(x, src: str = "float32") -> tuple:
@@ -103,10 +115,7 @@ def mxfp8_kernel_model(x, src: str = "float32") -> tuple:
     float32 values, or bf16 bit patterns (uint16) with ``src="bfloat16"``;
     blocks of 32 along the last axis.  Returns ``(codes uint8 like x, scales
     uint8 [..., K/32])``."""
-    x, ub, key, amax = _model_blocks(x, src)
-    field = (amax >> np.uint32(23)).astype(np.int32)
-    sb = np.where(amax == 0, 127, np.maximum(field - 8, 0)).astype(np.uint32)
-    mult = ((np.uint32(254) - sb) << np.uint32(23)).view(np.float32)
+    x, ub, key, sb, mult = _model_blocks(x, src, FP8_E4M3_EMAX)
     with np.errstate(over="ignore", invalid="ignore", under="ignore"):
         w = e4m3_convert_model(ub.view(np.float32) * mult[:, None])
     nan = (np.uint32(0x80000000) - key.view(np.uint32)).view(np.int32) < 0
@@ -120,10 +129,7 @@ def mxfp4_reference(x) -> tuple:
     float32 input, or of the decoded values of bf16 bit patterns (a uint16
     array or a bf16 :class:`ClArray`): ``(packed codes [..., K/2], scales)``,
     blocks along the last axis."""
-    if isinstance(x, ClArray):
-        x = x.array
-    x = np.asarray(x)
-    return to_mxfp4(from_bf16_bits(x) if x.dtype == np.uint16 else x.astype(np.float32, copy=False))
+    return _reference(to_mxfp4, x)
 
 
 def e2m1_convert_model(y: np.ndarray) -> np.ndarray:
@@ -154,10 +160,7 @@ def mxfp4_kernel_model(x, src: str = "float32") -> tuple:
     float32 values, or bf16 bit patterns (uint16) with ``src="bfloat16"``;
     blocks of 32 along the last axis.  Returns ``(packed codes uint8 [...,
     K/2], scales uint8 [..., K/32])`` like :func:`to_mxfp4`."""
-    x, ub, key, amax = _model_blocks(x, src)
-    field = (amax >> np.uint32(23)).astype(np.int32)
-    sb = np.where(amax == 0, 127, np.maximum(field - 2, 0)).astype(np.uint32)
-    mult = ((np.uint32(254) - sb) << np.uint32(23)).view(np.float32)
+    x, ub, key, sb, mult = _model_blocks(x, src, FP4_E2M1_EMAX)
     with np.errstate(over="ignore", invalid="ignore", under="ignore"):
         w = e2m1_convert_model(ub.view(np.float32) * mult[:, None])
     nan = (np.uint32(0x80000000) - key.view(np.uint32)).view(np.int32) < 0
@@ -266,7 +269,7 @@ class MxFp8Quantizer(_MxQuantizer):
     ``X`` (``rows·K`` of the source type; bf16 as the uint16-storage bf16
     ClArray) is the input, ``codes`` (``"float8_e4m3fn"``), ``scales`` (uint8,
     ``rows·K/32``, row-major) and ``packed`` (uint32, ``rows·K/128``, the
-    layout of :func:`~cekirdekler_amd.ops.gemm.pack_mx_scales`) the outputs;
+    layout of :func:`~cekirdekler_amd.ops.tiling.pack_mx_scales`) the outputs;
     ``packed`` exists when rows % 64 = 0 and K % 128 = 0 and is None
     otherwise.  Arrays passed in are adopted (``x``: an input that already
     lives in a ClArray, e.g. another kernel's output); their transfer flags
@@ -282,9 +285,9 @@ class MxFp8Quantizer(_MxQuantizer):
 class MxFp4Quantizer(_MxQuantizer):
     """``[rows][K]`` fp32 or bf16 → MXFP4 through ``compute()``
     (``kernels/mx4_quantize.hip``), bit for bit
-    :func:`~cekirdekler_amd.ops.gemm.to_mxfp4`: :class:`MxFp8Quantizer` with
+    :func:`~cekirdekler_amd.ops.codecs.to_mxfp4`: :class:`MxFp8Quantizer` with
     ``codes`` a ``"float4_e2m1fn_x2"`` array of ``rows·K/2`` bytes (two
-    elements per byte, :func:`~cekirdekler_amd.ops.gemm.pack_fp4`).  A block
+    elements per byte, :func:`~cekirdekler_amd.ops.codecs.pack_fp4`).  A block
     with a NaN has the scale byte ``0xFF``.  The pack compute is the MXFP8
     one, so the cruncher needs ``library("mx4_quantize", "mx_quantize")``."""
 

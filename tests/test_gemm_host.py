@@ -1,6 +1,10 @@
 """Host-side logic of the GEMM ops (no GPU): object set-up for every tile,
 the shell decomposition, tile orders and the guards that run before any
 kernel does."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -245,3 +249,86 @@ def test_bf16_encoder_matches_torch_bit_for_bit():
 
 def test_aux_bf16_codec_on_cpu_device():
     bf16_aux_codec_case(ck.ClPlatforms.all().cpus(True))
+
+
+# ---------------------------------------------------- constructed state, imports
+
+GOLDEN_STATE = os.path.join(os.path.dirname(__file__), "golden", "gemm_state.json")
+STATE_ARRAYS = ("A", "B", "C", "SA", "SB", "_SAp", "_SBp", "W", "counters")
+
+
+def gemm_state_cases():
+    """``(id, class, shape, keywords)``: every class × every tile of its table
+    at M = BM, N = 2·BN, K = twice the class's K multiple; bf16 also with
+    ``split_k=2`` on the split-K tiles, and its exchange tiles once more at a
+    K long enough for a nonzero ``exchange_shift``."""
+    from cekirdekler_amd.ops import gemm
+
+    cases = []
+    for cls, table, kmult in ((gemm.GemmBf16, gemm.TILES, 64), (gemm.GemmF32, gemm.F32_TILES, 32),
+                              (gemm.GemmFp8, gemm.FP8_TILES, 128), (gemm.GemmMxFp8, gemm.MXFP8_TILES, 128),
+                              (gemm.GemmMxFp4, gemm.MXFP4_TILES, 256)):
+        for tile in sorted(table):
+            BM, BN = table[tile][:2]
+            cases.append((f"{cls.__name__}-{tile}", cls, (BM, 2 * BN, 2 * kmult), {"tile": tile}))
+            if cls is gemm.GemmBf16 and tile in gemm.SPLIT_K_TILES:
+                cases.append((f"{cls.__name__}-{tile}-sk2", cls, (BM, 2 * BN, 2 * kmult), {"tile": tile, "split_k": 2}))
+            if cls is gemm.GemmBf16 and tile in gemm.EXCHANGE_TILES:
+                cases.append((f"{cls.__name__}-{tile}-k1024", cls, (BM, 2 * BN, 1024), {"tile": tile}))
+                cases.append((f"{cls.__name__}-{tile}-k1024-shift2", cls, (BM, 2 * BN, 1024),
+                              {"tile": tile, "exchange_shift": 2, "handover_spin_limit": -1}))
+    return cases
+
+
+def gemm_state(g) -> dict:
+    """What a constructor leaves behind, as JSON can hold it."""
+    s = {k: getattr(g, k) for k in ("kernel", "global_range", "split_k", "exchange", "exchange_shift", "row_major_c")}
+    s["geom"] = None if g.geom is None else list(g.geom)
+    s["dims"] = g.dims.array.tolist()
+    s["arrays"] = {}
+    for name in STATE_ARRAYS:
+        a = getattr(g, name, None)
+        if a is not None:
+            s["arrays"][name] = {"N": a.N, "dtype": a.dtype_name, "read": a.read, "write": a.write,
+                                 "elements_per_work_item": a.elements_per_work_item}
+    s["sha256"] = {name: hashlib.sha256(getattr(g, name).array.tobytes()).hexdigest()
+                   for name in ("A", "B", "SA", "SB") if hasattr(g, name)}
+    return s
+
+
+def test_constructed_state_matches_parent(cpu_cr):
+    """Every class × tile builds the object the per-class constructors built
+    before they were folded into one: tests/golden/gemm_state.json was written
+    by those, with ``seed=0``."""
+    with open(GOLDEN_STATE) as f:
+        want = json.load(f)
+    cases = gemm_state_cases()
+    assert sorted(want) == sorted(c[0] for c in cases)
+    for cid, cls, shape, kw in cases:
+        assert gemm_state(cls(*shape, cruncher=cpu_cr, seed=0, **kw)) == want[cid], cid
+
+
+# every name tests/, bench/, bench.py, tools/ and __graft_entry__.py take from
+# cekirdekler_amd.ops.gemm (``from … import X`` and ``gemm.X``), by home module
+GEMM_NAMES = ("TILES", "TILE_WAVES", "GEMM_LIBS", "F32_TILES", "FP8_TILES", "MXFP8_TILES", "MXFP8_TILE_WAVES",
+              "MXFP4_TILES", "MXFP4_TILE_WAVES", "SPLIT_K_TILES", "EXCHANGE_TILES", "EXCHANGE_SHIFT", "GemmBf16",
+              "GemmF32", "GemmFp8", "GemmMxFp8", "GemmMxFp4", "decode_operand", "library")
+CODEC_NAMES = ("to_bf16_bits", "from_bf16_bits", "to_fp8_e4m3_bits", "from_fp8_e4m3_bits", "e8m0_to_f64",
+               "to_fp4_e2m1_codes", "from_fp4_e2m1_codes", "pack_fp4", "unpack_fp4", "to_mxfp8", "from_mxfp8",
+               "to_mxfp4", "from_mxfp4")
+TILING_NAMES = ("tile_to_rows", "rows_to_tile", "tile_coords", "untile", "pack_mx_scales", "unpack_mx_scales")
+
+
+def test_gemm_module_keeps_its_import_surface():
+    from cekirdekler_amd.ops import codecs, gemm, quantize, tiling
+
+    for name in GEMM_NAMES + CODEC_NAMES + TILING_NAMES + ("MX_BLOCK", "FP4_E2M1_EMAX", "ROW_MAJOR_TILES"):
+        assert hasattr(gemm, name), name
+    for home, names in ((codecs, CODEC_NAMES), (tiling, TILING_NAMES)):
+        for name in names:
+            assert getattr(gemm, name) is getattr(home, name), name
+            assert getattr(home, name).__module__ == home.__name__, name
+    assert gemm.MX_BLOCK == codecs.MX_BLOCK == quantize.MX_BLOCK == 32 and gemm.FP4_E2M1_EMAX == codecs.FP4_E2M1_EMAX == 2
+    for name in ("to_mxfp8", "to_mxfp4", "from_bf16_bits", "pack_fp4"):  # the quantisers' codecs are the same objects
+        assert getattr(quantize, name) is getattr(codecs, name), name
+    assert gemm.MxFp8Quantizer is quantize.MxFp8Quantizer and gemm.MxFp4Quantizer is quantize.MxFp4Quantizer
