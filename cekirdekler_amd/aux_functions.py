@@ -58,15 +58,20 @@ __device__ inline float cek_wave_sum(float v) {
 #endif
 """,
     # workgroup reduction through LDS; every work item gets the sum.
-    # scratch must hold blockDim.x floats (declare it __shared__ in the kernel)
+    # scratch must hold blockDim.x floats (declare it __shared__ in the kernel).
+    # Any local size: a step folds the upper floor(m/2) of the m live
+    # elements onto the lower ones and keeps ceil(m/2), so an odd middle
+    # element stays live (at a power of two this is the plain halving tree)
     "block_sum": r"""
 __device__ inline float cek_block_sum(float v, float* scratch) {
   const int t = (int)get_local_id(0), n = (int)get_local_size(0);
   scratch[t] = v;
   __syncthreads();
-  for (int s = n / 2; s > 0; s >>= 1) {
-    if (t < s) scratch[t] += scratch[t + s];
+  for (int m = n; m > 1;) {
+    const int s = (m + 1) >> 1;
+    if (t < m - s) scratch[t] += scratch[t + s];
     __syncthreads();
+    m = s;
   }
   const float r = scratch[0];
   __syncthreads();

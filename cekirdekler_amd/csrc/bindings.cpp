@@ -240,6 +240,9 @@ PYBIND11_MODULE(_cek, m) {
     return py::make_tuple(ranges, history);
   });
   m.attr("HISTORY_DEPTH") = kHistoryDepth;
+  // device-side enqueue: queue levels (the parent's included) and records per level
+  m.attr("DYN_LEVELS") = kDynLevels;
+  m.attr("DYN_CAP") = kDynCap;
 
   py::class_<ArraySpec>(m, "ArraySpec")
       .def(py::init<>())

@@ -110,20 +110,6 @@ static std::string regex_replace_all(const std::string& s, const std::string& pa
   return std::regex_replace(s, std::regex(pat), rep);
 }
 
-// OpenCL-C → HIP C++ (best effort; the reference's kernels are OpenCL C).
-static std::string translate_opencl(const std::string& src) {
-  std::string s = strip_comments(src);
-  s = regex_replace_all(s, R"((^|[^\w])(__kernel|kernel)(\s+void\s))", "$1__global__$3");
-  s = regex_replace_all(s, R"((^|[^\w])__global(?![\w]))", "$1");
-  s = regex_replace_all(s, R"((^|[^\w])global(\s+[\w]))", "$1$2");
-  s = regex_replace_all(s, R"((^|[^\w])(__local|local)(\s+))", "$1__shared__$3");
-  s = regex_replace_all(s, R"((^|[^\w])(__constant|constant)(\s+))", "$1const$3");
-  s = regex_replace_all(s, R"((^|[^\w])(__private|private)(\s+))", "$1$3");
-  s = regex_replace_all(s, R"(barrier\s*\([^)]*\))", "__syncthreads()");
-  s = regex_replace_all(s, R"(mem_fence\s*\([^)]*\))", "__threadfence()");
-  return "#define CEK_OPENCL_DIALECT 1\n" + s;
-}
-
 static size_t match_paren(const std::string& s, size_t open) {
   int depth = 0;
   for (size_t i = open; i < s.size(); ++i) {
@@ -134,6 +120,84 @@ static size_t match_paren(const std::string& s, size_t open) {
   }
   return std::string::npos;
 }
+
+// String and character literals (found the way strip_comments finds them)
+// are taken out of `s` and replaced by "\x02<index>\x02", which no rewrite
+// rule matches; put_literals puts them back.
+static std::string take_literals(const std::string& s, std::vector<std::string>& lits) {
+  std::string o;
+  size_t i = 0, n = s.size();
+  while (i < n) {
+    if (s[i] != '"' && s[i] != '\'') {
+      o += s[i++];
+      continue;
+    }
+    const size_t b = i;
+    const char q = s[i++];
+    while (i < n && s[i] != q) {
+      if (s[i] == '\\') ++i;
+      ++i;
+    }
+    i = std::min(n, i + 1);
+    o += '\x02' + std::to_string(lits.size()) + '\x02';
+    lits.push_back(s.substr(b, i - b));
+  }
+  return o;
+}
+
+static std::string put_literals(const std::string& s, const std::vector<std::string>& lits) {
+  std::string o;
+  for (size_t i = 0; i < s.size(); ++i) {
+    if (s[i] != '\x02') {
+      o += s[i];
+      continue;
+    }
+    const size_t e = s.find('\x02', i + 1);
+    o += lits[std::stoul(s.substr(i + 1, e - i - 1))];
+    i = e;
+  }
+  return o;
+}
+
+// Calls `name(...)` of the functions `names` (a regex alternation of whole
+// identifiers) become `rep`; the argument list ends at its matching paren.
+static std::string replace_calls(const std::string& s, const std::string& names, const std::string& rep) {
+  const std::regex re(R"((^|[^\w])()" + names + R"()\s*\()");
+  std::string o;
+  auto at = s.cbegin();
+  std::smatch m;
+  while (std::regex_search(at, s.cend(), m, re)) {
+    const size_t name_pos = static_cast<size_t>(at - s.cbegin()) + static_cast<size_t>(m.position(2));
+    const size_t open = static_cast<size_t>(at - s.cbegin()) + static_cast<size_t>(m.position(0) + m.length(0)) - 1;
+    const size_t close = match_paren(s, open);
+    if (close == std::string::npos) break;
+    o.append(at, s.cbegin() + static_cast<std::ptrdiff_t>(name_pos));
+    o += rep;
+    at = s.cbegin() + static_cast<std::ptrdiff_t>(close + 1);
+  }
+  o.append(at, s.cend());
+  return o;
+}
+
+// OpenCL-C → HIP C++ (best effort; the reference's kernels are OpenCL C).
+// Only code is rewritten: literals are left as they are, and barrier /
+// mem_fence are matched as whole identifiers.  The rewrites put
+// CEK_OPENCL_DIALECT ahead of the prelude, which declares the builtins.
+static std::string translate_opencl(const std::string& src) {
+  std::vector<std::string> lits;
+  std::string s = take_literals(strip_comments(src), lits);
+  s = regex_replace_all(s, R"((^|[^\w])(__kernel|kernel)(\s+void\s))", "$1__global__$3");
+  s = regex_replace_all(s, R"((^|[^\w])__global(?![\w]))", "$1");
+  s = regex_replace_all(s, R"((^|[^\w])global(\s+[\w]))", "$1$2");
+  s = regex_replace_all(s, R"((^|[^\w])(__local|local)(\s+))", "$1__shared__$3");
+  s = regex_replace_all(s, R"((^|[^\w])(__constant|constant)(\s+))", "$1const$3");
+  s = regex_replace_all(s, R"((^|[^\w])(__private|private)(\s+))", "$1$3");
+  s = replace_calls(s, "barrier", "__syncthreads()");
+  s = replace_calls(s, "read_mem_fence|write_mem_fence|mem_fence", "__threadfence()");
+  return put_literals(s, lits);
+}
+
+static const char* kDialectDefine = "#define CEK_OPENCL_DIALECT 1\n";
 
 static int count_params(const std::string& inside) {
   std::string t;
@@ -205,14 +269,29 @@ static const char* kGpuPrelude = R"CEK(
 #define cek_global_group_id() ((long long)blockIdx.x + __cek_off / (long long)blockDim.x)
 #define cek_local_group_id() ((long long)blockIdx.x)
 #define cek_local_num_groups() ((long long)gridDim.x)
+// HIP has no atomicAdd on long long (it has Max and Min); the CPU device
+// does.  Two's complement: the unsigned add is the signed one.
+__device__ inline long long atomicAdd(long long* p, long long v) {
+  return (long long)atomicAdd((unsigned long long*)p, (unsigned long long)v);
+}
 #ifdef CEK_OPENCL_DIALECT
 typedef unsigned int uint; typedef unsigned char uchar; typedef unsigned short ushort; typedef unsigned long ulong;
-__device__ inline float native_sqrt(float x) { return __fsqrt_rn(x); }
-__device__ inline float native_rsqrt(float x) { return rsqrtf(x); }
-__device__ inline float native_exp(float x) { return __expf(x); }
-__device__ inline float native_sin(float x) { return __sinf(x); }
-__device__ inline float native_cos(float x) { return __cosf(x); }
-__device__ inline float native_divide(float a, float b) { return __fdividef(a, b); }
+// native_*: macros over functions of another name.  A device function that
+// is itself called native_sqrt (native_exp, ...) mangles like the OpenCL
+// builtin, and the AMDGPU backend's library-call pass then replaces it by
+// the full-precision function, whatever its body says.
+__device__ inline float __cek_native_sqrt(float x) { return __fsqrt_rn(x); }
+__device__ inline float __cek_native_rsqrt(float x) { return rsqrtf(x); }
+__device__ inline float __cek_native_exp(float x) { return __expf(x); }
+__device__ inline float __cek_native_sin(float x) { return __sinf(x); }
+__device__ inline float __cek_native_cos(float x) { return __cosf(x); }
+__device__ inline float __cek_native_divide(float a, float b) { return __fdividef(a, b); }
+#define native_sqrt(x) __cek_native_sqrt(x)
+#define native_rsqrt(x) __cek_native_rsqrt(x)
+#define native_exp(x) __cek_native_exp(x)
+#define native_sin(x) __cek_native_sin(x)
+#define native_cos(x) __cek_native_cos(x)
+#define native_divide(a, b) __cek_native_divide(a, b)
 __device__ inline float mad(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ inline float clamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 __device__ inline int atomic_add(int* p, int v) { return atomicAdd(p, v); }
@@ -277,7 +356,11 @@ extern "C" float cosf(float) noexcept __attribute__((__simd__("notinbranch")));
 extern "C" float expf(float) noexcept __attribute__((__simd__("notinbranch")));
 extern "C" float logf(float) noexcept __attribute__((__simd__("notinbranch")));
 #endif
-template <class T> static inline T atomicAdd(T* p, T v) {
+// The value's type is the pointee's, as with HIP's overloads: the second
+// argument is not deduced, so atomicAdd(&ull, 1) and atomicMax(&f, 2) convert
+// it.  The generic compare-exchange covers float and double as well.
+template <class T> struct __CekSame { using type = T; };
+template <class T> static inline T atomicAdd(T* p, typename __CekSame<T>::type v) {
   T old, nv; __atomic_load(p, &old, __ATOMIC_RELAXED);
   do { nv = old + v; } while (!__atomic_compare_exchange(p, &old, &nv, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST));
   return old;
@@ -285,9 +368,20 @@ template <class T> static inline T atomicAdd(T* p, T v) {
 static inline int atomicAdd(int* p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
 static inline unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
 static inline long long atomicAdd(long long* p, long long v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-template <class T> static inline T atomicMax(T* p, T v) { T o = *p; while (o < v && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {} return o; }
-template <class T> static inline T atomicMin(T* p, T v) { T o = *p; while (o > v && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {} return o; }
-template <class T> static inline T atomicExch(T* p, T v) { return __atomic_exchange_n(p, v, __ATOMIC_SEQ_CST); }
+template <class T> static inline T atomicMax(T* p, typename __CekSame<T>::type v) {
+  T o; __atomic_load(p, &o, __ATOMIC_RELAXED);
+  while (o < v && !__atomic_compare_exchange(p, &o, &v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
+  return o;
+}
+template <class T> static inline T atomicMin(T* p, typename __CekSame<T>::type v) {
+  T o; __atomic_load(p, &o, __ATOMIC_RELAXED);
+  while (o > v && !__atomic_compare_exchange(p, &o, &v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {}
+  return o;
+}
+template <class T> static inline T atomicExch(T* p, typename __CekSame<T>::type v) {
+  T o; __atomic_exchange(p, &v, &o, __ATOMIC_SEQ_CST);
+  return o;
+}
 static inline void __threadfence() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }
 // Work-group barrier on the CPU device: every work-item of a group is a
 // fiber (ucontext) on one host thread; __syncthreads() yields to the group
@@ -431,7 +525,9 @@ static std::string dyn_prelude(const std::vector<std::string>& children) {
 }
 
 std::string gpu_rewrite(const std::string& src) {
-  std::string s = is_opencl_dialect(src) ? translate_opencl(src) : strip_comments(src);
+  const bool dialect = is_opencl_dialect(src);
+  std::string s = dialect ? translate_opencl(src) : strip_comments(src);
+  const std::string prelude = std::string(dialect ? kDialectDefine : "") + kGpuPrelude;
   // hiprtc supplies the HIP runtime itself.
   s = regex_replace_all(s, R"(#\s*include\s*[<"]hip/hip_runtime\.h[>"])", "");
   const bool dyn = uses_device_enqueue(s);
@@ -456,15 +552,16 @@ std::string gpu_rewrite(const std::string& src) {
       os << "extern \"C\" __global__ void __cek_dispatch_" << k.sig.name << "(" << inside
          << (params.empty() ? "" : ", ")
          << "long long __cek_off, long long __cek_gsize, void* __cek_q, int __cek_level) {\n"
-         << "  __CekQueue* q = (__CekQueue*)__cek_q;\n"
-         << "  const int cnt = min(q->count[__cek_level], CEK_DYN_CAP);\n"
-         << "  const long long stride = (long long)gridDim.x * blockDim.x;\n"
-         << "  for (int r = 0; r < cnt; ++r) {\n"
-         << "    const __CekRec rec = q->recs[__cek_level][r];\n"
-         << "    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < rec.n; i += stride) {\n"
-         << "      switch (rec.child) {\n";
+         << "  __CekQueue* __cek_qp = (__CekQueue*)__cek_q;\n"
+         << "  const int __cek_cnt = min(__cek_qp->count[__cek_level], CEK_DYN_CAP);\n"
+         << "  const long long __cek_stride = (long long)gridDim.x * blockDim.x;\n"
+         << "  for (int __cek_r = 0; __cek_r < __cek_cnt; ++__cek_r) {\n"
+         << "    const __CekRec __cek_rec = __cek_qp->recs[__cek_level][__cek_r];\n"
+         << "    for (long long __cek_i = (long long)blockIdx.x * blockDim.x + threadIdx.x; __cek_i < __cek_rec.n;\n"
+         << "         __cek_i += __cek_stride) {\n"
+         << "      switch (__cek_rec.child) {\n";
       for (size_t c = 0; c < children.size(); ++c)
-        os << "        case " << c << ": " << children[c] << "(i, rec.param" << names
+        os << "        case " << c << ": " << children[c] << "(__cek_i, __cek_rec.param" << names
            << ", __cek_q, __cek_level); break;\n";
       os << "        default: break;\n      }\n    }\n  }\n}\n";
       dispatchers += os.str();
@@ -482,7 +579,7 @@ std::string gpu_rewrite(const std::string& src) {
     }
     if (!k.has_extern_c) s.insert(k.global_pos, "extern \"C\" ");
   }
-  if (!dyn) return std::string(kGpuPrelude) + "#line 1\n" + s;
+  if (!dyn) return prelude + "#line 1\n" + s;
   // children get the queue and their own level (enqueues go one deeper)
   static const std::regex child_re(R"(__cek_child__\s+void\s+([A-Za-z_]\w*)\s*\()");
   std::vector<std::pair<size_t, size_t>> parens;
@@ -493,19 +590,20 @@ std::string gpu_rewrite(const std::string& src) {
   }
   for (auto it = parens.rbegin(); it != parens.rend(); ++it)
     s.insert(it->second, ", void* __cek_q, int __cek_level");
-  return std::string(kGpuPrelude) + dyn_prelude(children) + "#line 1\n" + s + "\n// ---- dispatchers ----\n" +
+  return prelude + dyn_prelude(children) + "#line 1\n" + s + "\n// ---- dispatchers ----\n" +
          dispatchers;
 }
 
 std::string cpu_rewrite(const std::string& src) {
-  std::string s = is_opencl_dialect(src) ? translate_opencl(src) : strip_comments(src);
+  const bool dialect = is_opencl_dialect(src);
+  std::string s = dialect ? translate_opencl(src) : strip_comments(src);
   s = regex_replace_all(s, R"(#\s*include\s*[<"]hip/[\w\.]+[>"])", "");
   auto sites = find_sites(s);
   for (auto it = sites.rbegin(); it != sites.rend(); ++it)
     if (!it->has_extern_c) s.insert(it->global_pos, "extern \"C\" ");
   bool barriers = std::regex_search(s, std::regex(R"(__syncthreads\s*\()"));
   std::ostringstream os;
-  os << kCpuPrelude << "#line 1\n" << s << "\n// ---- runners ----\n";
+  os << (dialect ? kDialectDefine : "") << kCpuPrelude << "#line 1\n" << s << "\n// ---- runners ----\n";
   std::set<std::string> seen;
   for (auto& k : sites) {
     if (!seen.insert(k.sig.name).second) continue;

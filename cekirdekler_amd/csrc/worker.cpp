@@ -780,7 +780,10 @@ void* Worker::dyn_queue(hipStream_t s) {
   if (!q) {
     set_device();
     CEK_HIP(hipMalloc(&q, kDynQueueBytes));
-    CEK_HIP(hipMemset(q, 0, kDynHeaderBytes));
+    // on the queue's own stream: a memset on the null stream is not ordered
+    // with these (non-blocking) streams and could clear the level counts after
+    // the first parent had enqueued
+    CEK_HIP(hipMemsetAsync(q, 0, kDynHeaderBytes, s));
   }
   return q;
 }

@@ -78,7 +78,7 @@ def test_device_enqueue_rewrite_and_compile():
     out = cek.gpu_rewrite(DYN_SRC)
     assert "__cek_dispatch_parent(float* x, long long __cek_off, long long __cek_gsize, void* __cek_q, int __cek_level)" in out
     assert "void fill(long long id, long long param, float* x, void* __cek_q, int __cek_level)" in out
-    assert "case 1: fill2(i, rec.param, x, __cek_q, __cek_level)" in out
+    assert "case 1: fill2(__cek_i, __cek_rec.param, x, __cek_q, __cek_level)" in out
     ok, code, log = cek.compile_gpu(DYN_SRC, [], "gfx950")
     assert ok, log
     # plain sources are untouched by the dynamic path
