@@ -3,7 +3,7 @@
 
 * ``direct``: the reference's way (Worker.cs:833-860) — every GPU uploads the
   whole array over its own PCIe link;
-* ``staged``: the runtime's xGMI fan-out (``Cores::stage_peer_reads``) —
+* ``staged``: the runtime's xGMI fan-out (``PeerTraffic::stage_reads``) —
   every GPU uploads 1/D of it, then pulls the other D−1 chunks from its
   peers' replicas (``hipMemcpyPeerAsync`` over the point-to-point links),
   event-ordered, no host sync.

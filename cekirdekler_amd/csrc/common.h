@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -47,6 +48,17 @@ enum DevType : int { kCPU = 1, kGPU = 2, kACC = 4 };
 inline double now_ms() {
   using namespace std::chrono;
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// Chunk k of `bytes` cut into `parts` chunks of one size, that size rounded up
+// to a multiple of `align`: (byte offset, length).  The last chunks may be
+// short or empty.  The xGMI read fan-out aligns to 4 KiB, the distributed
+// split upload to the element size.
+inline std::pair<uint64_t, uint64_t> byte_chunk(uint64_t bytes, int parts, uint64_t align, int k) {
+  uint64_t chunk = (bytes + parts - 1) / parts;
+  chunk = (chunk + align - 1) / align * align;
+  const uint64_t off = std::min<uint64_t>(k * chunk, bytes);
+  return {off, std::min<uint64_t>(chunk, bytes - off)};
 }
 
 // Element-type codes shared with Python (ClArray dtype); sizes in bytes.

@@ -20,13 +20,26 @@
 // times are exchanged through an Exchanger, so every rank derives the
 // identical next split.  Optional RCCL data plane: broadcast `read` arrays
 // from rank 0 and all-gather written slices into every replica.
+//
+// Cores is the scheduler: balancer state, mode switches, compute() with its
+// failover (cores.cpp) and the three execution shapes (cores_run.cpp).  Spans
+// and timeline (spans.h), peer traffic (peer.h), compute graphs (graphs.h),
+// deferred downloads (downloads.h), the schedule log (sched_log.h) and the
+// shell GEMM's dims (shell_gemm.h) are parts that own and free their state.
 #pragma once
 #include <condition_variable>
+#include <deque>
 #include <map>
 #include <mutex>
 
 #include "balancer.h"
 #include "dist.h"
+#include "downloads.h"
+#include "graphs.h"
+#include "peer.h"
+#include "sched_log.h"
+#include "shell_gemm.h"
+#include "spans.h"
 #include "worker.h"
 
 namespace cek {
@@ -151,15 +164,11 @@ class Cores {
 
   int error_code() const { return error_code_; }
   const std::string& error_message() const { return error_; }
-  std::vector<KernelSig> kernels() const;
-  int num_devices() const { return static_cast<int>(workers_.size()); }
-  int num_global_devices() const { return global_devices_; }
-  const DeviceInfo& device(int i) const { return workers_.at(i)->dev(); }
   double build_ms() const { return build_ms_; }
 
   void compute(const ComputeCall& call);
 
-  // ---- modes ----
+  // ---- modes and knobs ----
   bool enqueue_mode() const { return enqueue_mode_; }
   void set_enqueue_mode(bool on);
   bool async_enqueue = false;
@@ -168,181 +177,49 @@ class Cores {
   // with fine_grained: this compute's marker is deferred (Worker::defer_marker)
   // until flush_markers(); the device pool sets it per task
   bool defer_marker = false;
-  void flush_markers(int dev) { workers_.at(dev)->flush_markers(); }
   bool smooth = true;
   bool serial = false;  // run devices one after another (isolated timings)
   // Repeat loops with at least this many launches per device are captured
   // into a hipGraph and replayed (0 disables graphs).
   int graph_min_launches = 8;
-  // Gate every stream of local device `device` (-1: all) on `ev`: work
-  // enqueued afterwards starts only once ev.trigger() (ClUserEvent.cs:102-117).
-  void gate(class UserEvent& ev, int device);
-  void set_time_scale(int device, double scale);  // injected heterogeneity (tests/bench)
-  // injected fixed cost per compute on a device (ms of host time spent before
-  // its work, counted in its measured time): tests of the overhead-aware split
-  void set_time_offset(int device, double ms);
   // Opt-in overhead-aware balancing (balancer.h predict_split): fits
   // t = a + b·range per device and may leave a device out; single-process
   // jobs only (the law stays the default and the distributed rule).
   bool balancer_predictor = false;
-  const FitState* fit_state(int id) const {
-    auto it = state_.find(id);
-    return it == state_.end() ? nullptr : &it->second.fit;
-  }
+  void set_time_scale(int device, double scale);  // injected heterogeneity (tests/bench)
+  // injected fixed cost per compute on a device (ms of host time spent before
+  // its work, counted in its measured time): tests of the overhead-aware split
+  void set_time_offset(int device, double ms);
+  // ---- device-time spans, downloads, host-memory release ----
+  bool device_spans = true;  // CEK_DEVICE_SPANS=0: host wall clock instead
+  bool single_device_spans = false;  // spans with one device in the job too (CEK_SINGLE_DEVICE_SPANS=1)
+  // async enqueue computes' downloads after the next compute's uploads
+  // (CEK_DEFER_DOWNLOADS=0: in each compute's own order)
+  bool deferred_downloads = true;
+  // a system-scope release marker after kernels that may store into
+  // zero-copy host memory (per compute in sync mode, once per batch when
+  // enqueue mode is left); CEK_ZC_RELEASE=0 turns it off
+  bool zc_release = true;
   // ---- failure handling ----
-  // A disabled device gets no range; the balancer runs over the others.
-  void set_device_enabled(int device, bool on);
-  bool device_enabled(int device) const { return enabled_.at(device); }
-  // Make the next `count` computes on local device `device` fail (tests).
-  void inject_failure(int device, int count);
   // When a device fails during compute(): disable it and re-run the call on
   // the remaining devices (single-process jobs only).
   bool auto_failover = false;
-  // ---- schedule recording (pipeline dependency checks) ----
-  // Every transfer / kernel / event edge the pipelines issue is appended as
-  // (device, op, logical stream, first work item, work items, event), by the
-  // call that issues it (Cores::Ordering, cores.cpp).  The logical stream is
-  // the id of the Lane it ran on (worker.h: main_lane_id, compute_lane_id,
-  // pipe_lane_id).
-  struct SchedOp {
-    int device;
-    std::string op;  // h2d | kernel | d2h | rec | wait
-    int stream;
-    long long begin, count;
-    int event;
-  };
+  // ---- recording ----
+  // schedule recording (sched_log.h)
+  using SchedOp = cek::SchedOp;
   bool record_schedule = false;
-  std::vector<SchedOp> schedule() {
-    std::lock_guard<std::mutex> g(sched_mu_);
-    return sched_;
-  }
-  void clear_schedule() {
-    std::lock_guard<std::mutex> g(sched_mu_);
-    sched_.clear();
-  }
-  int failovers() const { return failovers_; }
-  void set_dynamic_lds(unsigned bytes);
-  // device-side enqueue (cek_enqueue): child levels per parent launch, and
-  // the errors counted on the devices so far (syncs)
-  void set_device_enqueue_levels(int levels);
-  // debug checks: guard tails on new buffers, synchronous checked launches
-  void set_debug_checks(bool on);
-  bool debug_checks() const { return debug_checks_; }
-  // downloads of pinned / registered host memory by a copy kernel instead
-  // of hipMemcpyAsync (Worker::kernel_d2h; env CEK_KERNEL_D2H)
-  void set_kernel_d2h(bool on) {
-    for (auto& w : workers_) w->kernel_d2h = on;
-  }
-  bool kernel_d2h() const { return !workers_.empty() && workers_[0]->kernel_d2h.load(); }
-  // kernel profiling timestamps (Worker::kernel_times_on)
-  void set_kernel_times(bool on) {
-    for (auto& w : workers_) w->kernel_times_on = on;
-  }
-  bool kernel_times_on() const { return !workers_.empty() && workers_[0]->kernel_times_on.load(); }
-  std::vector<std::pair<std::string, double>> kernel_times(int dev) { return workers_.at(dev)->kernel_times(); }
-  // CUs reserved per GPU for copy kernels (Worker::set_cu_reserve); drains
-  // and re-creates the streams
-  void set_copy_cus(int n) {
-    std::lock_guard<std::recursive_mutex> g(call_mu_);
-    if (capturing_) throw Error("copy CUs cannot change during a graph capture");
-    for (auto& w : workers_) w->set_cu_reserve(n);
-  }
-  int copy_cus() const { return workers_.empty() ? 0 : workers_[0]->cu_reserve(); }
-  // identity of device w's host thread pool (0 for a GPU): equal across
-  // crunchers that share one (CpuPool::shared)
-  uintptr_t cpu_pool_id(int w) const {
-    return (w < 0 || w >= static_cast<int>(workers_.size())) ? 0 : workers_[w]->cpu_pool_id();
-  }
-  uint64_t kernel_d2h_bytes() const {
-    uint64_t b = 0;
-    for (auto& w : workers_) b += w->kernel_d2h_bytes();
-    return b;
-  }
-  int device_enqueue_errors();
-  // ---- device timeline ----
   // With record_timeline on, the kernels of every compute are bracketed by
   // timing hipEvents on the stream they run on (host clock on the CPU
   // device).  timeline() waits for the recorded work and returns
   // (device, compute id, begin ms, end ms) per span, relative to the first
   // span of that device, then clears the list.
-  struct TimelineSpan {
-    int device, compute_id;
-    double begin_ms, end_ms;
-    double abs_begin_ms, abs_end_ms;  // host clock (event_host_ms): comparable across devices
-  };
+  using TimelineSpan = cek::TimelineSpan;
   bool record_timeline = false;
-  std::vector<TimelineSpan> timeline();
-
-  // ---- state ----
-  bool has_state(int id) const { return state_.count(id) > 0; }
-  std::vector<long long> ranges(int id) const;
-  std::vector<long long> references(int id) const;
-  std::vector<double> benchmarks(int id) const;
-  std::vector<std::vector<double>> history(int id) const;
-  void set_state(int id, const std::vector<long long>& ranges,
-                 const std::vector<std::vector<double>>& history, const std::vector<double>& bench);
-  std::vector<int> compute_ids() const;
-  int last_compute_id() const { return last_id_; }
-  ComputeRecord last_record() const { return last_record_; }
-
-  long long markers_reached();
-  long long markers_issued();
-  std::pair<int, uint64_t> last_marker(int dev) const { return workers_.at(dev)->last_marker(); }
-  uint64_t marker_word(int dev, int slot) { return workers_.at(dev)->marker_word(slot); }
-  void finish();  // synchronise every stream of every device
-  void release_array(uint64_t uid);
-  uint64_t device_bytes(int i) const { return workers_.at(i)->bytes_allocated(); }
-  // Raw device pointer of a cached replica (allocates if needed).
-  uint64_t device_pointer(int i, const ArraySpec& a);
-  void upload(int i, const ArraySpec& a);    // whole array H2D (sync)
-  void download(int i, const ArraySpec& a);  // whole array D2H (sync)
-  // Keep-resident all-gather inside one process: every device's slice of
-  // `a` (by the ranges of compute id `id`) is copied into every other
-  // device's replica, GPU↔GPU as peer copies over xGMI (no host bounce).
-  // Event-ordered (no host sync in enqueue mode); later computes and
-  // downloads wait for the copies on the device.
-  void share_slices(int id, const ArraySpec& a, long long local_range);
-  // ---- peer topology (SURVEY §5.8 item 4) ----
-  // Distinct GPU ordinals of this Cores' devices and hipDeviceCanAccessPeer
-  // among them; access is enabled at construction when they span >= 2 GPUs.
-  const std::vector<int>& peer_ordinals() const { return peer_ordinals_; }
-  const std::vector<std::vector<int>>& peer_matrix() const { return peer_matrix_; }
-  const std::string& p2p_path() const { return p2p_path_; }
-  bool can_peer(int w1, int w2) const;  // local workers: same GPU, or peer access on
-  void copy_between(int src_dev, const ArraySpec& src, int dst_dev, const ArraySpec& dst,
-                    uint64_t bytes);  // device→device (peer/xGMI) copy, sync
-
-  // ---- compute graphs (hipGraph capture of a sequence of computes) ----
-  // capture_begin() puts every GPU's main stream into (relaxed) stream
-  // capture; the computes that follow are recorded, not run: enqueue-mode
-  // semantics (split frozen, no host syncs), main stream only, no markers,
-  // device spans, peer-read staging or nested repeat graphs.  capture_end()
-  // instantiates one graph per GPU and returns its id; graph_launch(id, n)
-  // replays it n times back to back on each GPU's main stream — one
-  // hipGraphLaunch per GPU per replay instead of one host call per kernel
-  // and copy.  Host transfers inside the graph read / write the host
-  // arrays at replay time (pinned or registered memory only).  Buffers must
-  // exist before capture: run the computes once first.
-  void capture_begin();
-  int capture_end();
-  void graph_launch(int id, int times, bool sync);
-  // Host-resident GEMM C = A·Bᵀ streamed in square shells of P row panels
-  // (csrc/shell_gemm.cpp): uploads, kernels and downloads of consecutive
-  // shells overlap; C comes back shell by shell.  Synchronous.
-  void gemm_host_shells(int local_dev, const std::string& kernel, const ArraySpec& A, const ArraySpec& B,
-                        const ArraySpec& C, int M, int N, int K, int panels, int group_m, int BM, int BN, int L);
-  void graph_destroy(int id);
-  bool capturing() const { return capturing_; }
-
   // ---- distributed ----
-  void set_distributed(std::shared_ptr<Exchanger> ex, std::shared_ptr<Comm> comm,
-                       int global_devices, int global_base);
   bool dist_gather_writes = false;
   bool dist_broadcast_reads = false;
   // identical host copies on every rank: each uploads 1/N, RCCL all-gathers
   bool dist_split_reads = false;
-  int global_base() const { return global_base_; }
-
   // ---- xGMI fan-out of full `read` arrays ----
   // The reference uploads every `read` array to every device
   // (Worker.cs:833-860): D PCIe copies contending for the host.  With two or
@@ -353,6 +230,8 @@ class Cores {
   // point-to-point xGMI mesh, one link per peer pair, ordered by events (no
   // host sync).  PCIe carries the array once instead of D times.
   bool peer_reads = true;
+  uint64_t peer_read_min_bytes = 1u << 20;
+  // ---- pipelines ----
   // event pipeline: issue each blob's D2H on its compute stream
   bool pipeline_writes_on_compute_stream = false;
   // event pipeline: every blob's D2H on one write stream (blob order)
@@ -376,6 +255,7 @@ class Cores {
   // driver pipeline: blob uploads on the main stream (one in-order chain of
   // copies, as the event pipeline's), each blob's queue waiting for its own
   bool driver_reads_on_main_stream = true;
+  // ---- host threads and waits ----
   // a mixed CPU + GPU call runs the participant with the largest share on
   // the calling thread (off, the default: the CPU device).  Measured on the
   // wave frame: the GPU inline left the CPU a 1 % share and 0.044 ms per
@@ -388,16 +268,137 @@ class Cores {
   // GPU workers wait for their streams by sleeping on a blocking-sync event
   // (off by default; CEK_SLEEP_WAITS=1)
   bool sleep_waits = false;
-  uint64_t peer_read_min_bytes = 1u << 20;
+  // ---- per-worker switches ----
+  void set_dynamic_lds(unsigned bytes);
+  // device-side enqueue (cek_enqueue): child levels per parent launch, and
+  // the errors counted on the devices so far (syncs)
+  void set_device_enqueue_levels(int levels);
+  int device_enqueue_errors();
+  // debug checks: guard tails on new buffers, synchronous checked launches
+  void set_debug_checks(bool on);
+  bool debug_checks() const { return debug_checks_; }
+  // downloads of pinned / registered host memory by a copy kernel instead
+  // of hipMemcpyAsync (Worker::kernel_d2h; env CEK_KERNEL_D2H)
+  void set_kernel_d2h(bool on) {
+    for (auto& w : workers_) w->kernel_d2h = on;
+  }
+  bool kernel_d2h() const { return !workers_.empty() && workers_[0]->kernel_d2h.load(); }
+  uint64_t kernel_d2h_bytes() const {
+    uint64_t b = 0;
+    for (auto& w : workers_) b += w->kernel_d2h_bytes();
+    return b;
+  }
+  // kernel profiling timestamps (Worker::kernel_times_on)
+  void set_kernel_times(bool on) {
+    for (auto& w : workers_) w->kernel_times_on = on;
+  }
+  bool kernel_times_on() const { return !workers_.empty() && workers_[0]->kernel_times_on.load(); }
+  std::vector<std::pair<std::string, double>> kernel_times(int dev) { return workers_.at(dev)->kernel_times(); }
+  // CUs reserved per GPU for copy kernels (Worker::set_cu_reserve); drains
+  // and re-creates the streams
+  void set_copy_cus(int n) {
+    std::lock_guard<std::recursive_mutex> g(call_mu_);
+    if (capturing_) throw Error("copy CUs cannot change during a graph capture");
+    for (auto& w : workers_) w->set_cu_reserve(n);
+  }
+  int copy_cus() const { return workers_.empty() ? 0 : workers_[0]->cu_reserve(); }
+
+  // ---- queries ----
+  std::vector<KernelSig> kernels() const;
+  int num_devices() const { return static_cast<int>(workers_.size()); }
+  int num_global_devices() const { return global_devices_; }
+  int global_base() const { return global_base_; }
+  const DeviceInfo& device(int i) const { return workers_.at(i)->dev(); }
+  uint64_t device_bytes(int i) const { return workers_.at(i)->bytes_allocated(); }
+  // identity of device w's host thread pool (0 for a GPU): equal across
+  // crunchers that share one (CpuPool::shared)
+  uintptr_t cpu_pool_id(int w) const {
+    return (w < 0 || w >= static_cast<int>(workers_.size())) ? 0 : workers_[w]->cpu_pool_id();
+  }
+  // ---- balancer state ----
+  bool has_state(int id) const { return state_.count(id) > 0; }
+  std::vector<long long> ranges(int id) const;
+  std::vector<long long> references(int id) const;
+  std::vector<double> benchmarks(int id) const;
+  std::vector<std::vector<double>> history(int id) const;
+  void set_state(int id, const std::vector<long long>& ranges,
+                 const std::vector<std::vector<double>>& history, const std::vector<double>& bench);
+  std::vector<int> compute_ids() const;
+  int last_compute_id() const { return last_id_; }
+  ComputeRecord last_record() const { return last_record_; }
+  const FitState* fit_state(int id) const {
+    auto it = state_.find(id);
+    return it == state_.end() ? nullptr : &it->second.fit;
+  }
+  // ---- failures ----
+  // A disabled device gets no range; the balancer runs over the others.
+  void set_device_enabled(int device, bool on);
+  bool device_enabled(int device) const { return enabled_.at(device); }
+  // Make the next `count` computes on local device `device` fail (tests).
+  void inject_failure(int device, int count);
+  int failovers() const { return failovers_; }
+  // ---- recordings ----
+  std::vector<SchedOp> schedule() { return sched_.ops(); }
+  void clear_schedule() { sched_.clear(); }
+  std::vector<TimelineSpan> timeline();
+  // ---- markers ----
+  long long markers_reached();
+  long long markers_issued();
+  std::pair<int, uint64_t> last_marker(int dev) const { return workers_.at(dev)->last_marker(); }
+  uint64_t marker_word(int dev, int slot) { return workers_.at(dev)->marker_word(slot); }
+  void flush_markers(int dev) { workers_.at(dev)->flush_markers(); }
+  // ---- peer topology (SURVEY §5.8 item 4) ----
+  // Distinct GPU ordinals of this Cores' devices and hipDeviceCanAccessPeer
+  // among them; access is enabled at construction when they span >= 2 GPUs.
+  const std::vector<int>& peer_ordinals() const { return peer_.ordinals(); }
+  const std::vector<std::vector<int>>& peer_matrix() const { return peer_.matrix(); }
+  const std::string& p2p_path() const { return peer_.path(); }
+  bool can_peer(int w1, int w2) const { return peer_.can_peer(w1, w2); }
+
+  // ---- operations ----
+  void finish();  // synchronise every stream of every device
+  void release_array(uint64_t uid);
+  // Gate every stream of local device `device` (-1: all) on `ev`: work
+  // enqueued afterwards starts only once ev.trigger() (ClUserEvent.cs:102-117).
+  void gate(class UserEvent& ev, int device);
+  // Raw device pointer of a cached replica (allocates if needed).
+  uint64_t device_pointer(int i, const ArraySpec& a);
+  void upload(int i, const ArraySpec& a);    // whole array H2D (sync)
+  void download(int i, const ArraySpec& a);  // whole array D2H (sync)
+  // Keep-resident all-gather inside one process: every device's slice of
+  // `a` (by the ranges of compute id `id`) is copied into every other
+  // device's replica, GPU↔GPU as peer copies over xGMI (no host bounce).
+  // Event-ordered (no host sync in enqueue mode); later computes and
+  // downloads wait for the copies on the device.
+  void share_slices(int id, const ArraySpec& a, long long local_range);
+  void copy_between(int src_dev, const ArraySpec& src, int dst_dev, const ArraySpec& dst,
+                    uint64_t bytes);  // device→device (peer/xGMI) copy, sync
+  // ---- compute graphs (hipGraph capture of a sequence of computes, graphs.h) ----
+  void capture_begin();
+  int capture_end();
+  void graph_launch(int id, int times, bool sync);
+  void graph_destroy(int id);
+  bool capturing() const { return capturing_; }
+  // Host-resident GEMM C = A·Bᵀ streamed in square shells of P row panels
+  // (csrc/shell_gemm.cpp): uploads, kernels and downloads of consecutive
+  // shells overlap; C comes back shell by shell.  Synchronous.
+  void gemm_host_shells(int local_dev, const std::string& kernel, const ArraySpec& A, const ArraySpec& B,
+                        const ArraySpec& C, int M, int N, int K, int panels, int group_m, int BM, int BN, int L);
+  void set_distributed(std::shared_ptr<Exchanger> ex, std::shared_ptr<Comm> comm,
+                       int global_devices, int global_base);
 
  private:
-  PhaseBarrier* phase_ = nullptr;  // set while a hazardous compute runs
+  // ---- compute(): cores.cpp ----
+  void compute_once(const ComputeCall& call, struct DeviceFailure* failed);
+  void balance(struct BalancerState& st, bool first, long long G, long long step);
+  void restore_capture_state();  // the modes capture_begin saved (graphs_.saved())
+  // ---- the execution shapes: cores_run.cpp ----
+  struct Ordering;  // issues and logs what the three run_* shapes enqueue
   bool collective(const ComputeCall& c) const;
   void run_device(int w, const ComputeCall& c, long long ref, long long range, bool pipelined,
                   double* out_ms, uint64_t* h2d, uint64_t* d2h);
   void run_device_body(int w, const ComputeCall& c, long long ref, long long range, bool pipelined,
                   double* out_ms, uint64_t* h2d, uint64_t* d2h);
-  struct Ordering;  // issues and logs what the three run_* shapes enqueue (cores.cpp)
   void run_3phase(Worker& wk, int gidx, const ComputeCall& c, long long ref, long long range,
                   uint64_t* h2d, uint64_t* d2h);
   void run_event_pipeline(Worker& wk, int gidx, const ComputeCall& c, long long ref,
@@ -408,158 +409,55 @@ class Cores {
                       long long range);
   void launch_kernels_body(Worker& wk, hipStream_t s, const ComputeCall& c, long long ref,
                            long long range);
-  struct PendingSpan {
-    int device, compute_id;
-    hipEvent_t begin, end;      // GPU: timing events (device epoch: first span's begin)
-    double host_begin, host_end;  // CPU device: host clock
-  };
-  std::mutex tl_mu_;
-  std::vector<PendingSpan> pending_spans_;
   void full_reads(Worker& wk, hipStream_t s, const ComputeCall& c, uint64_t* h2d);
-  // per-call peer fan-out: which arrays were staged, and per local worker the
-  // event its streams wait on before using them
-  struct PeerEvents {
-    hipEvent_t up = nullptr;      // this GPU's chunk uploaded
-    hipEvent_t pulled = nullptr;  // every other chunk pulled into this GPU
-  };
-  std::vector<PeerEvents> peer_ev_;
-  std::vector<hipEvent_t> peer_ready_;  // every participant pulled: kernels may modify the staged arrays
-  std::vector<char> staged_arr_;  // by array index, for the current call
-  std::vector<char> staged_dev_;  // by local worker, for the current call
-  uint64_t stage_peer_reads(const ComputeCall& c, const std::vector<long long>& ranges,
-                            std::vector<uint64_t>& h2d);
-  // peer topology
-  std::vector<int> peer_ordinals_;
-  std::vector<std::vector<int>> peer_matrix_;
-  std::string p2p_path_ = "none";
-  std::vector<int> ord_index_;  // local worker -> index into peer_ordinals_ (-1: CPU device)
-  void init_peer_topology();
-  // per-call device→device accounting
-  struct D2DCount {
-    uint64_t bytes = 0, xgmi = 0, local = 0, staged = 0;
-    bool pcie_fallback = false;
-  } d2d_;
-  void count_d2d(int ws, int wd, uint64_t bytes);
-  uint64_t d2d_copy(int ws, int wd, char* dst, const char* src, uint64_t bytes, hipStream_t s, int stream_worker);
-  // keep-resident gather (ArraySpec::gather): kernels-done event per worker,
-  // copies-done event per GPU worker; later work waits on every copies-done
-  // event while gather_pending_
-  std::vector<hipEvent_t> kdone_, pushed_;
-  bool gather_pending_ = false;
-  bool all_gpu_ = true;  // every local device is a GPU (device-time spans feed the balancer)
-  bool call_gathers_ = false;  // the running call gathers in-process
-  hipEvent_t gather_event(std::vector<hipEvent_t>& v, int w);
-  void wait_gather(Worker& wk, hipStream_t s);
-  uint64_t issue_gather(const ComputeCall& c, const struct BalancerState& st, const std::vector<int>& arrays,
-                        const std::vector<std::vector<std::pair<long long, long long>>>* owned = nullptr);
+  bool defer_downloads(const Worker& wk) const;
+  // issues wk's deferred downloads (downloads_) and the span ends that
+  // follow them (spans_); `next` and `c` as in DeferredDownloads::flush
+  void flush_downloads(Worker& wk, hipStream_t next = nullptr, const ComputeCall* c = nullptr);
+  // the scheduler's modes as the parts take them
+  SpanModes span_modes() const {
+    return {device_spans, single_device_spans, all_gpu_, global_devices_, enqueue_mode_, async_enqueue};
+  }
+  PeerView peer_view() const { return {enabled_, global_base_, enqueue_mode_}; }
 
-  std::vector<std::unique_ptr<Worker>> workers_;
+  PhaseBarrier* phase_ = nullptr;  // set while a hazardous compute runs
+  // one compute()/state access at a time per Cores (Python releases the GIL
+  // during compute, so two threads may call into the same cruncher)
+  mutable std::recursive_mutex call_mu_;
   std::map<int, BalancerState> state_;
   std::vector<double> time_scale_;
   std::vector<double> time_offset_;
   std::vector<bool> enabled_;
-  // one compute()/state access at a time per Cores (Python releases the GIL
-  // during compute, so two threads may call into the same cruncher)
-  mutable std::recursive_mutex call_mu_;
-  std::mutex sched_mu_;
-  std::vector<SchedOp> sched_;
-  void log_op(int gidx, const char* op, int stream, long long begin, long long count, int event = -1) {
-    if (!record_schedule) return;
-    std::lock_guard<std::mutex> g(sched_mu_);
-    sched_.push_back({gidx, op, stream, begin, count, event});
-  }
   std::vector<int> inject_;
   int failovers_ = 0;
   bool debug_checks_ = false;
-  void compute_once(const ComputeCall& call, struct DeviceFailure* failed);
-  void balance(struct BalancerState& st, bool first, long long G, long long step);
   std::string error_;
   int error_code_ = 0;
   double build_ms_ = 0;
   bool enqueue_mode_ = false;
   bool capturing_ = false;
+  bool all_gpu_ = true;  // every local device is a GPU (device-time spans feed the balancer)
   bool sleep_this_call_ = false;  // compute_once: GPU waits of this call sleep
-  std::vector<void*> shell_dims_;         // gemm_host_shells: per-kernel dims, per worker
-  std::vector<size_t> shell_dims_cap_;
-  std::vector<std::vector<int>> shell_dims_host_;  // what shell_dims_ holds (re-uploaded only on change)
-  std::vector<void*> shell_dims_pin_;               // pinned staging for that upload
-  void restore_capture_state();  // the modes capture_begin saved
-  struct CaptureSaved {
-    bool device_spans, peer_reads, async_enqueue, fine_grained, enqueue_mode, record_timeline;
-    int graph_min_launches;
-    bool kernel_times;
-  } cap_saved_{};
-  std::map<int, std::vector<hipGraphExec_t>> graphs_;  // id -> one exec per local worker (null: CPU)
-  // buffers each worker handed out while capturing: (uid, pointer) — a graph
-  // replays those pointers, so graph_launch refuses to run once any of them
-  // was released or reallocated
-  std::vector<std::vector<std::pair<uint64_t, void*>>> cap_logs_;
-  std::map<int, std::vector<std::vector<std::pair<uint64_t, void*>>>> graph_bufs_;
-  int next_graph_id_ = 1;
   double enqueue_t0_ = 0;
   int last_id_ = 0;
-  // ---- device-time spans for the balancer ----
-  // Each GPU device's work in a compute is bracketed by a pair of timing
-  // hipEvents on the stream it starts and ends on; the balancer gets the
-  // device time between them (hipEventElapsedTime) instead of host wall
-  // clock.  Sync mode reuses pair 0; enqueue mode takes a fresh pair per
-  // compute and, when the mode is left, credits each device with the union
-  // of its spans (so devices of one process re-balance by their own device
-  // time, not the shared wall clock).
-  struct DevSpans {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-    int used = 0;
-    hipEvent_t gap_a = nullptr, gap_b = nullptr;  // phase-barrier idle gap
-    bool gap = false;
-    hipStream_t batch = nullptr;  // enqueue mode: stream of the open batch span
-  };
-  std::vector<DevSpans> spans_;
- public:
-  bool device_spans = true;  // CEK_DEVICE_SPANS=0: host wall clock instead
-  // async enqueue computes' downloads after the next compute's uploads
-  // (CEK_DEFER_DOWNLOADS=0: in each compute's own order)
-  bool deferred_downloads = true;
-  bool single_device_spans = false;  // spans with one device in the job too (CEK_SINGLE_DEVICE_SPANS=1)
-  // a system-scope release marker after kernels that may store into
-  // zero-copy host memory (per compute in sync mode, once per batch when
-  // enqueue mode is left); CEK_ZC_RELEASE=0 turns it off
-  bool zc_release = true;
- private:
-  bool spans_on() const;
-  bool one_span_per_batch() const;
-  void close_batch_spans();
-  void span_begin(Worker& wk, hipStream_t s);
-  void span_end(Worker& wk, hipStream_t s);
-  double span_ms(int w);              // sync mode: the last span (stream drained)
-  double enqueue_spans_ms(int w);     // enqueue mode: union of the spans so far
-  // Async enqueue mode: a compute's downloads are issued after the NEXT
-  // compute's uploads (or when the batch ends).  A stream's copies go to an
-  // SDMA queue that other streams share and that runs in submission order:
-  // a download, which waits for its kernel, would hold back every later
-  // compute's upload behind it, and the computes would run one after the
-  // other instead of side by side (rocprofv3 trace, profiles/r5/README.md).
-  struct PendingD2H {
-    hipStream_t s;
-    ArraySpec a;
-    uint64_t begin, count;
-  };
-  struct PendingSpanEnd {
-    hipStream_t s;
-    int index;
-  };
-  std::vector<std::vector<PendingD2H>> pending_d2h_;          // per local device
-  std::vector<std::vector<PendingSpanEnd>> pending_span_end_;  // per local device
-  std::vector<std::vector<hipEvent_t>> order_events_;          // per local device (flush ordering)
-  bool defer_downloads(const Worker& wk) const;
-  bool must_flush_before(const Worker& wk, hipStream_t s, const ComputeCall& c) const;
-  void flush_downloads(Worker& wk, hipStream_t next = nullptr, const ComputeCall* c = nullptr);
   ComputeRecord last_record_;
   CoresConfig cfg_;
-
   std::shared_ptr<Exchanger> ex_;
   std::shared_ptr<Comm> comm_;
   int global_devices_ = 0;
   int global_base_ = 0;
+
+  // The workers, then the parts that work through them: destroyed in reverse
+  // order, so every part frees its events, graphs and buffers (each with its
+  // device current) while the workers and their streams still exist.
+  Workers workers_;
+  SchedLog sched_{record_schedule};
+  Spans spans_{workers_};
+  PeerTraffic peer_{workers_, sched_};
+  DeferredDownloads downloads_{workers_};
+  ComputeGraphs graphs_{workers_};
+  std::deque<ShellDims> shell_dims_;  // gemm_host_shells: per local device
 };
 
 }  // namespace cek
+

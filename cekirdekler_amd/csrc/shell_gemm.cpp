@@ -28,6 +28,28 @@
 
 namespace cek {
 
+ShellDims::~ShellDims() {
+  if (dev) {
+    (void)hipSetDevice(ordinal);
+    (void)hipFree(dev);
+  }
+  if (pin) host_free(pin);
+}
+
+void ShellDims::reserve(const Worker& wk, size_t bytes, hipStream_t up) {
+  if (cap >= bytes) return;
+  if (dev) {
+    CEK_HIP(hipStreamSynchronize(up));  // a previous call's kernels may still read the old block
+    (void)hipFree(dev);
+  }
+  dev = nullptr;
+  CEK_HIP(hipMalloc(&dev, bytes));
+  cap = bytes;
+  ordinal = wk.dev().ordinal;
+  if (pin) host_free(pin);
+  pin = host_alloc(bytes, 4096, nullptr);
+}
+
 void Cores::gemm_host_shells(int local_dev, const std::string& kernel, const ArraySpec& A, const ArraySpec& B,
                              const ArraySpec& C, int M, int N, int K, int panels, int group_m, int BM, int BN,
                              int L) {
@@ -49,8 +71,8 @@ void Cores::gemm_host_shells(int local_dev, const std::string& kernel, const Arr
   w.set_device();
 
   // per-kernel dims ([M', N', K, group_m, split_k, 0, 0, 0]) in device memory
-  if (shell_dims_.size() < workers_.size()) shell_dims_.resize(workers_.size(), nullptr);
-  if (shell_dims_cap_.size() < workers_.size()) shell_dims_cap_.resize(workers_.size(), 0);
+  if (shell_dims_.size() < workers_.size()) shell_dims_.resize(workers_.size());
+  ShellDims& sd = shell_dims_[local_dev];
   std::vector<int> dims(static_cast<size_t>(2 * panels) * 8, 0);
   for (int s = 0; s < panels; ++s) {
     int* r = &dims[static_cast<size_t>(2 * s) * 8];
@@ -59,32 +81,20 @@ void Cores::gemm_host_shells(int local_dev, const std::string& kernel, const Arr
     c[0] = s * PM, c[1] = PN, c[2] = K, c[3] = group_m, c[4] = 1;
   }
   const size_t dims_bytes = dims.size() * sizeof(int);
-  if (shell_dims_host_.size() < workers_.size()) shell_dims_host_.resize(workers_.size());
   hipStream_t up = w.main_stream();
-  if (shell_dims_host_[local_dev] != dims) {
+  if (sd.host != dims) {
     // the dims change only with the shape: uploaded (asynchronously, ahead of
     // the first panel on the upload stream the kernels wait on) when they do
-    if (shell_dims_cap_[local_dev] < dims_bytes) {
-      if (shell_dims_[local_dev]) {
-        CEK_HIP(hipStreamSynchronize(up));  // a previous call's kernels may still read the old block
-        (void)hipFree(shell_dims_[local_dev]);
-      }
-      shell_dims_[local_dev] = nullptr;
-      CEK_HIP(hipMalloc(&shell_dims_[local_dev], dims_bytes));
-      shell_dims_cap_[local_dev] = dims_bytes;
-      if (shell_dims_pin_.size() < workers_.size()) shell_dims_pin_.resize(workers_.size(), nullptr);
-      if (shell_dims_pin_[local_dev]) host_free(shell_dims_pin_[local_dev]);
-      shell_dims_pin_[local_dev] = host_alloc(dims_bytes, 4096, nullptr);
-    }
+    sd.reserve(w, dims_bytes, up);
     CEK_HIP(hipStreamSynchronize(up));  // the staging buffer may still feed an earlier copy
-    std::memcpy(shell_dims_pin_[local_dev], dims.data(), dims_bytes);
-    CEK_HIP(hipMemcpyAsync(shell_dims_[local_dev], shell_dims_pin_[local_dev], dims_bytes, hipMemcpyHostToDevice, up));
-    shell_dims_host_[local_dev] = dims;
+    std::memcpy(sd.pin, dims.data(), dims_bytes);
+    CEK_HIP(hipMemcpyAsync(sd.dev, sd.pin, dims_bytes, hipMemcpyHostToDevice, up));
+    sd.host = dims;
   }
   char* dA = static_cast<char*>(w.buffer(A));
   char* dB = static_cast<char*>(w.buffer(B));
   char* dC = static_cast<char*>(w.buffer(C));
-  int* dd = static_cast<int*>(shell_dims_[local_dev]);
+  int* dd = static_cast<int*>(sd.dev);
 
   const uint64_t a_panel = static_cast<uint64_t>(PM) * K, b_panel = static_cast<uint64_t>(PN) * K;  // elements
   uint64_t c_off = 0;  // elements of C before shell s

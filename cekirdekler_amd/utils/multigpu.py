@@ -144,7 +144,7 @@ def measure_peer_read_threshold(devices, sizes: Sequence[int] = PEER_READ_SIZES,
     ``direct`` — every GPU uploads the whole array over its own PCIe link
     (the reference, Worker.cs:833-860) — and ``staged`` — 1/D uploaded per
     GPU, the rest pulled from the peers' replicas over xGMI
-    (``Cores::stage_peer_reads``).  A tiny kernel reads the array on every
+    (``PeerTraffic::stage_reads``).  A tiny kernel reads the array on every
     GPU, so a call's time is the transfer; modes interleaved, median of
     ``calls``, every output checked.  Returns the sizes, both timings,
     ``crossover_bytes`` (:func:`pick_crossover`) and ``exact``."""

@@ -80,6 +80,31 @@ static void test_jit() {
   CHECK(is_opencl_dialect("__kernel void k(__global float* a) { a[0] = 1; }"));
 }
 
+// byte_chunk against the two splits it replaced: the read fan-out's (4 KiB
+// chunks) and the distributed split upload's (whole elements).
+static void test_byte_chunk() {
+  const uint64_t sizes[] = {0, 1, 4095, 4096, 4097, (1u << 20) + 3};
+  const uint64_t aligns[] = {4096, 1, 2, 4, 8};
+  for (uint64_t bytes : sizes)
+    for (int P : {1, 2, 3, 8})
+      for (uint64_t align : aligns)
+        for (int k = 0; k < P; ++k) {
+          uint64_t chunk = (bytes + P - 1) / P, off, len;
+          if (align == 4096) {  // stage_peer_reads
+            chunk = (chunk + 4095) / 4096 * 4096;
+            off = std::min<uint64_t>(k * chunk, bytes);
+            len = std::min<uint64_t>(chunk, bytes - off);
+          } else {  // full_reads with dist_split_reads
+            const int elem_size = static_cast<int>(align);
+            chunk = (chunk + elem_size - 1) / elem_size * elem_size;
+            off = std::min<uint64_t>(k * chunk, bytes);
+            len = std::min<uint64_t>(chunk, bytes - off);
+          }
+          const auto got = byte_chunk(bytes, P, align, k);
+          CHECK(got.first == off && got.second == len);
+        }
+}
+
 static void test_cores() {
   DeviceInfo cpu = cpu_info(2);
   std::vector<DeviceInfo> devs = {cpu, cpu};  // two logical CPU devices
@@ -198,6 +223,7 @@ static void test_cores() {
 int main() {
   test_balancer();
   test_jit();
+  test_byte_chunk();
   test_cores();
   if (failures) {
     std::fprintf(stderr, "%d check(s) failed\n", failures);

@@ -2,10 +2,49 @@
 members (NotImplementedException stubs in ClArray.cs:1105-1353; read-only
 queries work here, size changes are refused) and the usage-type-2 Cores
 mode switches / error state (Cores.cs:80-140)."""
+import json
+import os
+
 import numpy as np
 import pytest
 
 import cekirdekler_amd as ck
+
+GOLDEN_API = os.path.join(os.path.dirname(__file__), "golden", "cores_api.json")
+
+
+def cores_api_state() -> dict:
+    """The public names of every class the native extension exports, and the
+    plain bool / int / float attributes of a fresh CPU-device Cores."""
+    from cekirdekler_amd._native import cek
+
+    classes = {name: sorted(a for a in dir(obj) if not a.startswith("_"))
+               for name, obj in sorted(vars(cek).items()) if isinstance(obj, type)}
+    c = ck.Cores("cpu", "__global__ void k(float* a) { a[get_global_id(0)] += 1.0f; }", ["k"])
+    native = c.cruncher._cores
+    defaults = {}
+    for a in classes["Cores"]:
+        if a == "build_ms":  # a measurement, not a default
+            continue
+        v = getattr(native, a)
+        if type(v) in (bool, int, float):
+            defaults[a] = v
+    c.dispose()
+    return {"classes": classes, "cores_defaults": defaults}
+
+
+def test_native_api_is_pinned():
+    """The scheduler was split into owning parts behind an unchanged API:
+    tests/golden/cores_api.json was written by this function from the
+    extension built at the commit before the split, and the built extension
+    must still export exactly those names and defaults."""
+    with open(GOLDEN_API) as f:
+        want = json.load(f)
+    got = cores_api_state()
+    assert sorted(got["classes"]) == sorted(want["classes"])
+    for name in want["classes"]:
+        assert got["classes"][name] == want["classes"][name], name
+    assert got["cores_defaults"] == want["cores_defaults"]
 
 
 def test_clarray_list_queries():

@@ -189,7 +189,7 @@ def test_copy_engines_byte_exact_same_gpu(engine, nbytes):
 
 def test_gather_through_kernel_copy_engine():
     """The keep-resident gather with the copy-kernel engine forced: same
-    result as with SDMA (Cores::d2d_copy → peer_copy)."""
+    result as with SDMA (PeerTraffic::d2d_copy → peer_copy)."""
     from cekirdekler_amd._native import cek
 
     g0 = ck.ClPlatforms.all().gpus()[0]

@@ -1,5 +1,5 @@
 """The recorded pipeline schedules, tuple for tuple, against fixtures recorded
-before the pipelines moved onto one ordering primitive (csrc/cores.cpp,
+before the pipelines moved onto one ordering primitive (csrc/cores_run.cpp,
 `Ordering`): that refactor may not change a single logged operation.
 
 Every case runs on a fresh cruncher with an explicit queue concurrency (so

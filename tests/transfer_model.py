@@ -1,4 +1,4 @@
-"""Executable model of compute()'s data movement (csrc/cores.cpp), its probe
+"""Executable model of compute()'s data movement (csrc/cores_run.cpp, csrc/peer.cpp), its probe
 kernels, its case generators and the harness that runs one case against a
 backend.  tests/test_transfer_model.py is the CPU tier, tests/
 test_gpu_transfer_model.py the GPU tier; docs/API.md states the same rules
@@ -540,7 +540,7 @@ class Emulator:
         return up, down
 
     def _gather(self, arrs, ranges, references, enabled, offset) -> None:
-        """Cores::issue_gather: with two or more enabled devices, every
+        """PeerTraffic::issue_gather: with two or more enabled devices, every
         device's slice of a gather array goes into every other enabled
         device's replica (a CPU device's replica is the host array)."""
         f = self.faults
