@@ -8,6 +8,7 @@
 // byte-identical to what it was when this function lived in that file
 // (tools/kernel_identity.py).
 #pragma once
+#include "gemm8_out.h"
 #include "gemm_parts.h"
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -48,11 +49,19 @@ __device__ __forceinline__ void cek_static_for(F&& f) {
 // bytes and a K-tile of 128 B holds 256 k: two scaled instructions per
 // fragment pair, step s on the 16 B of read s with the scales of 128-k step
 // 2·kt + s.  Everything written in bytes stays as it is.
-template <int WM, int WN, int FM, int FN, int MODE, bool X128, bool MX = false, bool F4 = false>
+// OUT: what is stored.  GEMM8_OUT_F32 (the default): C as fp32, tile-major in
+// fragment order.  Otherwise (gemm8_out.h) `C` points to the row-major [M][N]
+// output in that mode's format, `SY` to its row-major scale bytes (MX modes)
+// and dims[5] selects the activation (0: none, 1: ReLU), a word the other
+// kernels do not read.  Nothing above the store depends on OUT, so the
+// accumulators are those of the plain kernel with the same tile.
+template <int WM, int WN, int FM, int FN, int MODE, bool X128, bool MX = false, bool F4 = false,
+          int OUT = GEMM8_OUT_F32>
 __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const uint8_t* __restrict__ A,
                                            const uint8_t* __restrict__ Bt, float* __restrict__ C, char* smem,
                                            long long off, const int* __restrict__ SAp = nullptr,
-                                           const int* __restrict__ SBp = nullptr) {
+                                           const int* __restrict__ SBp = nullptr,
+                                           uint8_t* __restrict__ SY = nullptr) {
   static_assert(MODE == 0 || MODE == 4, "MODE is 0 or 4");
   static_assert(!MX || (X128 && FM % 4 == 0 && FN % 4 == 0), "MX: scaled instruction, 64-row scale groups");
   static_assert(!F4 || MX, "F4: block-scaled only");
@@ -338,6 +347,12 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
     if (!g1) bar();  // equal barrier counts for both groups
   }
 
+  if constexpr (OUT != GEMM8_OUT_F32) {
+    __syncthreads();  // every wave is done with the operand stages: LDS is free
+    gemm8_store_out<FM, FN, OUT>(acc, smem, C, SY, N, dims[5] == 1, m0 + wr * 16 * FM, n0 + wc * 16 * FN, wave,
+                                 lane);
+    return;
+  }
   // C tile in fragment order (sgemm_bf16.hip): acc[i][j][r] is
   // C(row = wr·16FM + i·16 + fq·4 + r, col = wc·16FN + j·16 + fr), stored at
   // ((((wr·WN + wc)·FM + i)·FN + j)·64 + lane)·4 + r of the tile.

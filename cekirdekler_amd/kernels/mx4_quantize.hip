@@ -37,31 +37,6 @@
 #include "cek_kernel.h"
 #include "mx_quantize_parts.h"
 
-// 0xF in nibble `k` for the key of a NaN, else 0
-__device__ __forceinline__ u32 mx4q_nan_nibble(int key, int k) {
-  return (u32)((int)(0x80000000u - (u32)key) >> 31) & (0xFu << (4 * k));
-}
-
-// OR over the four lanes of a block (aligned quads), in every lane: quad_perm
-// [1,0,3,2], then quad_perm [2,3,0,1]
-__device__ __forceinline__ u32 mx4q_block_or(u32 m) {
-  m |= (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true);
-  return m | (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true);
-}
-
-// eight fp32 bit patterns scaled by 2^-e (`scale` = 2^e) and rounded to e2m1:
-// element i in nibble i
-__device__ __forceinline__ u32 mx4q_cvt8(const u32 (&f)[8], float scale) {
-  u32 w = 0;
-  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mxq_float(f[0]), mxq_float(f[1]), scale, 0);
-  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mxq_float(f[2]), mxq_float(f[3]), scale, 1);
-  w = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mxq_float(f[4]), mxq_float(f[5]), scale, 2);
-  return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(w, mxq_float(f[6]), mxq_float(f[7]), scale, 3);
-}
-
-// the byte the block stores: 0xFF when one of its elements is a NaN
-__device__ __forceinline__ u32 mx4q_stored_byte(u32 sb, u32 nan) { return mx4q_block_or(nan) ? 0xFFu : sb; }
-
 extern "C" __global__ __launch_bounds__(64) void cek_mx4_quantize_f32(const u32x4* x, u32* codes, u32* scales,
                                                                        CEK_HIDDEN) {
   const int lane = (int)threadIdx.x;

@@ -34,30 +34,6 @@
 #include "cek_kernel.h"
 #include "mx_quantize_parts.h"
 
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-// 0x80 in byte `k` for the key of a NaN, else 0
-__device__ __forceinline__ u32 mxq_nan_bit(int key, int k) {
-  return (u32)((int)(0x80000000u - (u32)key) >> 31) & (0x80u << (8 * k));
-}
-
-// The conversion's dword made the codec's.  Bytes whose low seven bits are all
-// ones came from a NaN (`nan`: 0x80 in that byte) or from a value that rounded
-// past 448: the latter become 0x7e under their sign, a NaN loses its sign.
-__device__ __forceinline__ u32 mxq_fix(u32 w, u32 nan) {
-  const u32 full = ((w & 0x7f7f7f7fu) + 0x01010101u) & 0x80808080u;
-  return (w - ((full & ~nan) >> 7)) & ~nan;
-}
-
-// four values scaled by 2^-e (`scale` = 2^e) and rounded to e4m3fn
-__device__ __forceinline__ u32 mxq_cvt4(float a, float b, float c, float d, float scale) {
-  s16x2 r = {0, 0};
-  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, a, b, scale, false);
-  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, c, d, scale, true);
-  return __builtin_bit_cast(u32, r);
-}
-
 extern "C" __global__ __launch_bounds__(64) void cek_mx_quantize_f32(const u32x4* x, u32* codes, u32* scales,
                                                                       CEK_HIDDEN) {
   const int lane = (int)threadIdx.x;

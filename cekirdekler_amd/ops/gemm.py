@@ -20,6 +20,8 @@ the import path for all of them.
 """
 from __future__ import annotations
 
+import weakref
+
 import numpy as np
 
 from ..arrays import ClArray
@@ -28,7 +30,7 @@ from .codecs import (FP4_E2M1_EMAX, MX_BLOCK, e8m0_to_f64, from_bf16_bits, from_
                      from_fp8_e4m3_bits, from_mxfp4, from_mxfp8, pack_fp4, to_bf16_bits, to_fp4_e2m1_codes,
                      to_fp8_e4m3_bits, to_mxfp4, to_mxfp8, unpack_fp4)
 from .library import library
-from .quantize import MxFp4Quantizer, MxFp8Quantizer, _src_name
+from .quantize import LOCAL as QUANTIZE_LOCAL, PACK_KERNEL, MxFp4Quantizer, MxFp8Quantizer, _src_name
 from .tiling import pack_mx_scales, rows_to_tile, tile_coords, tile_to_rows, unpack_mx_scales, untile  # noqa: F401
 
 # tile name -> (BM, BN, work-group size, kernel).  The production tiles and
@@ -159,6 +161,18 @@ MXFP4_TILES = {
 }
 MXFP4_TILE_WAVES = {"256x256pbx": (2, 4, 8, 4), "128x128": (2, 2, 4, 4)}
 
+# Output modes of the MX GEMMs (kernels/sgemm_mx_out.hip): (operand format,
+# tile, out) -> kernel.  The loop is the plain tile's, so the fp32 values that
+# are converted are the plain kernel's C bit for bit; Y is row-major [M][N].
+MX_OUTPUTS = ("bfloat16", "mxfp8", "mxfp4")
+MX_OUT_KERNELS = {(fmt, tile, out): f"cek_sgemm_{fmt}_{tile}_{'bf16' if out == 'bfloat16' else out}"
+                  for fmt, tiles in (("mxfp8", MXFP8_TILES), ("mxfp4", MXFP4_TILES))
+                  for tile in tiles for out in MX_OUTPUTS}
+MX_OUT_LIB = "sgemm_mx_out"
+# the pack compute of an output-mode call runs under the call's compute id plus this
+MX_OUT_PACK_ID = 0x4D70
+MX_ACTIVATIONS = {None: 0, "relu": 1}  # dims[5]
+
 # tiles whose kernel stores C row-major ([M][N]) instead of tile-major
 ROW_MAJOR_TILES = {"256x256pbr"}
 # tiles with a split-K kernel variant ("<kernel>_sk", arrays + W + counters)
@@ -238,11 +252,9 @@ class GemmBf16:
         self.A = ClArray(M * K // self.PER_ITEM, self.OPERAND_DTYPE)
         self.B = ClArray(N * K // self.PER_ITEM, self.OPERAND_DTYPE)
         scales = self._alloc_scales()
-        self.C = ClArray(M * N, np.float32)
         for a in (self.A, self.B, *scales):
             a.write = False
-        self.C.read = False
-        self.C.elements_per_work_item = BM * BN // (L * self.split_k)
+        self._alloc_output()
         self.extra = []
         if self.split_k > 1:
             # per-work-group partial tiles (device-only scratch: never transferred;
@@ -266,6 +278,19 @@ class GemmBf16:
         """Allocate what a format keeps beside ``A`` and ``B`` (the MX formats:
         their scale arrays); returns those of them the kernels only read."""
         return ()
+
+    def _alloc_output(self) -> None:
+        """Allocate what the kernel writes: C, one contiguous slice per device."""
+        self.C = ClArray(self.M * self.N, np.float32)
+        self.C.read = False
+        self.C.elements_per_work_item = self.BM * self.BN // (self.L * self.split_k)
+
+    def _output_flags(self, resident: bool) -> None:
+        """Transfer flags of the written arrays for one call."""
+        self.C.write = not resident
+
+    def _after_compute(self, compute_id: int, resident: bool) -> None:
+        """What a format runs behind the GEMM compute of a call."""
 
     def _fill_random(self, rng) -> None:
         """Uniform [−1, 1) values in the operands' format, A then B."""
@@ -350,7 +375,7 @@ class GemmBf16:
         self.A.elements_per_work_item = panel // ((self.N // self.BN) * self.L) if streamed else 1
         if self.split_k > 1:
             self.counters.read = first  # zeroed once; the kernel re-arms them
-        self.C.write = not resident
+        self._output_flags(resident)
         gran = self.granularity()
         if streamed:
             gran = self._group_work_items()
@@ -359,6 +384,7 @@ class GemmBf16:
             pipeline=streamed, pipeline_type=stream_event, pipeline_blobs=max(1, stream_blobs),
             granularity=gran)
         self._uploaded = True
+        self._after_compute(compute_id, resident)
 
     def _inputs(self, upload: bool) -> tuple:
         """The arrays a call reads (``upload``: this call sends them to the devices)."""
@@ -754,7 +780,26 @@ class GemmMxFp8(GemmBf16):
     codes, scales and packed scales stay resident and the next resident
     :meth:`run` uploads nothing for that operand; its host arrays are stale
     until :meth:`sync_operands`, which every host reference (``verify*``,
-    ``reference``) calls first."""
+    ``reference``) calls first.
+
+    Output modes (``kernels/sgemm_mx_out.hip``).  ``out="bfloat16"``,
+    ``"mxfp8"`` or ``"mxfp4"`` makes the kernel store the next layer's operand
+    instead of ``C``: ``Y``, row-major ``[M][N]`` (bf16 bit patterns, e4m3fn
+    codes, or ``[M][N/2]`` packed e2m1) and, for the MX outputs, ``SY``
+    (``[M][N/32]`` E8M0 bytes, blocks of 32 along N) and the packed scales
+    ``Yp``, which a pack compute behind the GEMM makes from ``SY`` (compute id
+    ``compute_id + MX_OUT_PACK_ID``; ``records`` holds both records).  The
+    loop is the plain tile's, so what is converted is the plain kernel's C
+    bit for bit, and the conversion is the host codec's bit for bit
+    (:func:`~cekirdekler_amd.ops.quantize.gemm_out_model`).  ``act="relu"``
+    (``x > 0 → x``, ``NaN → NaN``, all else ``→ +0``) is applied to the fp32
+    accumulator first and needs an output mode.  ``Y`` and ``SY`` carry C's
+    flags; being row-major, a device's range is a block of rows only in
+    whole tile groups, so on several devices the split unit is one tile
+    group, ``(M / BM) % group_m`` must be 0 and the outputs are keep-resident
+    gathered; one device takes a ragged last group too.  :meth:`result`
+    decodes what was stored; streaming and the shell paths raise
+    ``ValueError``.  :meth:`take_operand` hands the output to the next GEMM."""
 
     TILE_TABLE = MXFP8_TILES
     TILE_GEOM = MXFP8_TILE_WAVES
@@ -764,12 +809,97 @@ class GemmMxFp8(GemmBf16):
     OPERAND_DTYPE = "float8_e4m3fn"
     _to_mx = staticmethod(to_mxfp8)  # [rows][K] fp32 values -> (what A / B store, scale bytes)
 
+    FORMAT = "mxfp8"  # the output mode of a producer whose Y this class reads as an operand
+
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
-                 group_m: int = 4, wave_granularity: bool | None = None):
-        self._stale = set()  # operands quantised on the device whose host arrays are behind
+                 group_m: int = 4, wave_granularity: bool | None = None, out: str | None = None,
+                 act: str | None = None):
+        self._stale = set()  # operands made on the device whose host arrays are behind
         self._quantizers = {}
+        self._taken = {}  # operand name -> the output-mode GEMM whose Y / SY / packed arrays it is
+        self._consumers = []  # (weak reference to a GEMM that took this one's output, operand name)
+        if out is not None and out not in MX_OUTPUTS:
+            raise ValueError(f"out must be None or one of {MX_OUTPUTS} (got {out!r})")
+        if act not in MX_ACTIVATIONS:
+            raise ValueError(f"act must be None or 'relu' (got {act!r})")
+        if act is not None and out is None:
+            raise ValueError("act needs an output mode (out=...): the plain kernels store the accumulator as it is")
+        self.out, self.act = out, act
+        if out is not None:
+            self.LIBS = type(self).LIBS + (MX_OUT_LIB,)
         super().__init__(M, N, K, devices, tile, cruncher, fill, seed, group_m, wave_granularity=wave_granularity)
+        if out is None:
+            return
+        self.kernel = MX_OUT_KERNELS[self.FORMAT, tile, out]
+        self.dims.array[5] = MX_ACTIVATIONS[act]
+        if self.cr.number_of_devices > 1 and (M // self.BM) % max(1, group_m):
+            raise ValueError(f"an output mode on several devices needs whole tile groups: (M / {self.BM}) = "
+                             f"{M // self.BM} must be a multiple of group_m ({group_m})")
+
+    def _alloc_output(self) -> None:
+        if self.out is None:
+            return super()._alloc_output()
+        # Y row-major [M][N] in the output's format, for the MX outputs with
+        # its row-major scales SY [M][N/32] and their packed form: the trio of
+        # an A / B operand with K = N.  Per work item: a tile's share, under
+        # which a device's range of whole tile groups is one block of rows.
+        n, per_tile = self.M * self.N, self.BM * self.BN
+        self.C = None
+        self.SY = self.Yp = None
+        if self.out == "bfloat16":
+            self.Y = ClArray(n, "bfloat16")
+        elif self.out == "mxfp8":
+            self.Y = ClArray(n, "float8_e4m3fn")
+        else:
+            self.Y = ClArray(n // 2, "float4_e2m1fn_x2")
+        self._out_epw = [(self.Y, per_tile * self.Y.N // n // self.L)]
+        if self.out != "bfloat16":
+            self.SY = ClArray(n // MX_BLOCK, np.uint8)
+            self.Yp = ClArray(n // 128, np.uint32)
+            self._dims_pack = ClArray(np.array([self.M, self.N], np.int32))
+            self._out_epw.append((self.SY, per_tile // MX_BLOCK // self.L))
+        for a, epw in self._out_epw:
+            a.read = False
+            a.elements_per_work_item = epw
+        self.records = []
+
+    def _output_flags(self, resident: bool) -> None:
+        if self.out is None:
+            return super()._output_flags(resident)
+        gather = self.cr.number_of_devices > 1
+        for a, epw in self._out_epw:
+            a.read = a.partial_read = False
+            a.write, a.elements_per_work_item, a.gather_resident = not resident, epw, gather
+
+    def _after_compute(self, compute_id: int, resident: bool) -> None:
+        if self.out is None:
+            return
+        self.records = [self.cr.last_record()]
+        if self.Yp is not None:
+            # the packed scales a consumer reads, from the whole resident SY
+            # (the pack compute of _MxQuantizer.run)
+            gather = self.cr.number_of_devices > 1
+            d, p = self._dims_pack, self.Yp
+            self.SY.write = self.SY.gather_resident = False
+            self.SY.elements_per_work_item = 1
+            d.read, d.write = True, False
+            p.read = p.partial_read = False
+            p.write, p.elements_per_work_item, p.gather_resident = not resident, 1, gather
+            d.next_param(self.SY, p).compute(self.cr, compute_id + MX_OUT_PACK_ID, PACK_KERNEL, p.N, QUANTIZE_LOCAL)
+            self.records.append(self.cr.last_record())
+        for ref, name in self._consumers:  # their host copies of this output are behind again
+            g = ref()
+            if g is not None and g._taken.get(name) is self:
+                g._stale.add(name)
+
+    def granularity(self) -> int:
+        """:meth:`GemmBf16.granularity`; an output mode on several devices
+        splits in whole tile groups, so that every device's range is one block
+        of rows of the row-major ``Y`` and ``SY``."""
+        if self.out is not None and self.cr.number_of_devices > 1:
+            return self._group_work_items()
+        return super().granularity()
 
     def _alloc_scales(self) -> tuple:
         M, N, K = self.M, self.N, self.K
@@ -804,6 +934,8 @@ class GemmMxFp8(GemmBf16):
         return (self.dims, *(trio[n][0] for n in host), *(trio[n][1] for n in host))
 
     def _params(self) -> tuple:
+        if self.out is not None:  # Y and, for the MX outputs, SY in C's place
+            return (self.A, self.B, self._SAp, self._SBp, *(a for a, _ in self._out_epw))
         return self.A, self.B, self._SAp, self._SBp, self.C
 
     def run(self, compute_id: int = 1, resident: bool = True, stream_blobs: int = 0,
@@ -816,7 +948,55 @@ class GemmMxFp8(GemmBf16):
         if self._stale and not resident:
             raise ValueError(f"operand(s) {sorted(self._stale)} were quantised on the device and the host arrays are "
                              "stale: call sync_operands() before a run(resident=False)")
+        if self.out is not None and stream_blobs:
+            raise ValueError("an output mode (out=...) has no streamed path: stream_blobs must be 0")
+        if self.out is not None:
+            have = {k.split(":")[0] for k in self.cr.kernel_names}
+            for k in (self.kernel, PACK_KERNEL):
+                if k not in have:
+                    raise ClComputeError(f"the cruncher has no kernel {k!r}: it was built without "
+                                         f"library({MX_OUT_LIB!r}) or library('mx_quantize')")
+        for name in self._taken:  # shared with their producer, which sets its own flags for its calls
+            for a in ((self.A, self._SAp) if name == "A" else (self.B, self._SBp)):
+                a.write = a.gather_resident = a.partial_read = False
+                a.elements_per_work_item = 1
         super().run(compute_id, resident, stream_blobs, stream_event)
+
+    def take_operand(self, name: str, producer: "GemmMxFp8") -> None:
+        """Make the output of ``producer``, an MX GEMM with ``out`` equal to
+        this class's format, operand ``name`` of this GEMM: ``Y`` / ``SY`` and
+        the packed scales become ``A`` / ``SA`` (``B`` / ``SB``) and the packed
+        array the kernels read — the same :class:`ClArray` objects on the same
+        cruncher, so the resident replicas the producer wrote are the operand
+        and nothing is copied.  The residency rules are :meth:`quantize`'s:
+        the next resident :meth:`run` uploads nothing for the operand, its
+        host arrays are stale (again after every call of the producer) until
+        :meth:`sync_operands`, and ``run(resident=False)`` is refused while
+        they are."""
+        if name not in ("A", "B"):
+            raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
+        out = getattr(producer, "out", None)
+        if out != self.FORMAT:
+            raise ValueError(f"format mismatch: {type(self).__name__} takes a producer with out={self.FORMAT!r} "
+                             f"(got out={out!r})")
+        rows = self.M if name == "A" else self.N
+        if producer.M != rows:
+            raise ValueError(f"rows mismatch: operand {name} has {rows} rows, the producer's M is {producer.M}")
+        if producer.N != self.K:
+            raise ValueError(f"K mismatch: this GEMM's K is {self.K}, the producer's N is {producer.N}")
+        if producer.cr is not self.cr:
+            raise ValueError("cruncher mismatch: producer and consumer must run on the same ClNumberCruncher")
+        if name == "A":
+            self.A, self.SA, self._SAp = producer.Y, producer.SY, producer.Yp
+        else:
+            self.B, self.SB, self._SBp = producer.Y, producer.SY, producer.Yp
+        for k in [k for k in self._quantizers if k[0] == name]:  # they hold the arrays given up
+            del self._quantizers[k]
+        self._taken[name] = producer
+        producer._consumers = [(r, n) for r, n in producer._consumers
+                               if r() is not None and (r() is not self or n != name)]
+        producer._consumers.append((weakref.ref(self), name))
+        self._stale.add(name)
 
     def quantize(self, name: str, x, src: str | None = None, download: bool = False) -> None:
         """Quantise operand ``name`` (``"A"``: ``[M][K]``, ``"B"``: ``[N][K]``)
@@ -909,7 +1089,45 @@ class GemmMxFp8(GemmBf16):
         sc = torch.from_numpy(self._scales(name)).to(device)
         return (x.view(-1, self.K // MX_BLOCK, MX_BLOCK) * sc[..., None]).view(-1, self.K)
 
+    def result(self, download: bool = True) -> np.ndarray:
+        """:meth:`GemmBf16.result`.  In an output mode: what was stored,
+        decoded to fp32 row-major ``[M][N]`` (the MX outputs through
+        :func:`from_mxfp8` / :func:`from_mxfp4`); ``download`` fetches ``Y``
+        and ``SY`` from device 0, which holds them whole."""
+        if self.out is None:
+            return super().result(download)
+        if download:
+            for a, _ in self._out_epw:
+                self.cr.download(a, 0)
+        if self.out == "bfloat16":
+            return from_bf16_bits(self.Y.array).reshape(self.M, self.N)
+        decode, per = (from_mxfp8, 1) if self.out == "mxfp8" else (from_mxfp4, 2)
+        with np.errstate(over="ignore", invalid="ignore"):
+            return decode(self.Y.array.reshape(self.M, self.N // per),
+                          self.SY.array.reshape(self.M, self.N // MX_BLOCK)).astype(np.float32)
+
+    def verify(self, compute_id: int = 1, tiles_per_device: int = 8, seed: int = 1, host: bool = False) -> float:
+        """:meth:`GemmBf16.verify`.  In an output mode: ``max |Y − act(ref)| /
+        max |ref|`` over the whole decoded output against the float64
+        product, the output format's rounding included (of the order of 2^-9
+        for bf16, 2^-4 for MXFP8, 2^-2 for MXFP4): a plausibility figure, not
+        a check of the bits."""
+        if self.out is None:
+            return super().verify(compute_id, tiles_per_device, seed, host)
+        got = self.result(download=not host).astype(np.float64)
+        ref = self.reference()
+        if self.act == "relu":
+            ref = np.where(ref > 0, ref, np.where(np.isnan(ref), ref, 0.0))
+        return float(np.nanmax(np.abs(got - ref)) / max(float(np.nanmax(np.abs(ref))), 1e-30))
+
+    def verify_full(self, compute_id: int = 1, host: bool = False, device=None) -> tuple:
+        if self.out is None:
+            return super().verify_full(compute_id, host, device)
+        return self.verify(compute_id, host=host), self.tiles
+
     def _no_shells(self, *a, **k):
+        if self.out is not None:
+            raise ValueError("an output mode (out=...) has no shell paths")
         raise NotImplementedError(f"{type(self).__name__} has no shell paths: the shell streamer "
                                   "(csrc/shell_gemm.cpp) passes no scales")
 
@@ -949,6 +1167,7 @@ class GemmMxFp4(GemmMxFp8):
 
     TILE_TABLE = MXFP4_TILES
     TILE_GEOM = MXFP4_TILE_WAVES
+    FORMAT = "mxfp4"
     K_MULTIPLE = 256
     LIBS = ("sgemm_mxfp4", "mx4_quantize", "mx_quantize")
     OPERAND_DTYPE = "float4_e2m1fn_x2"

@@ -30,6 +30,10 @@ LIBRARY = {
     "sgemm_fp8": ["cek_sgemm_fp8_128x128", "cek_sgemm_fp8_256x256pb", "cek_sgemm_fp8_256x256pbx"],
     "sgemm_mxfp8": ["cek_sgemm_mxfp8_128x128", "cek_sgemm_mxfp8_256x256pbx"],
     "sgemm_mxfp4": ["cek_sgemm_mxfp4_128x128", "cek_sgemm_mxfp4_256x256pbx"],
+    # the MXFP8 / MXFP4 tiles with the next layer's operand as output (ops/gemm.py, out=...): row-major
+    # bf16, or MXFP8 / MXFP4 codes with row-major scales, blocks of 32 along N
+    "sgemm_mx_out": [f"cek_sgemm_{fmt}_{tile}_{out}" for fmt in ("mxfp8", "mxfp4")
+                     for tile in ("128x128", "256x256pbx") for out in ("bf16", "mxfp8", "mxfp4")],
     # device-side MXFP8 quantisation (ops/quantize.py): fp32 / bf16 → codes + scales, scale repack
     "mx_quantize": ["cek_mx_quantize_f32", "cek_mx_quantize_bf16", "cek_mx_pack_scales"],
     # device-side MXFP4 quantisation: fp32 / bf16 → packed e2m1 codes + scales (the repack is mx_quantize's)
@@ -53,6 +57,7 @@ ARITY = {
     **{k: 4 for k in LIBRARY["sgemm_fp8"]},
     **{k: 6 for k in LIBRARY["sgemm_mxfp8"]},  # dims, A, Bt, packed SA, packed SB, C
     **{k: 6 for k in LIBRARY["sgemm_mxfp4"]},  # the same six; A and Bt hold two e2m1 elements per byte
+    **{k: (6 if k.endswith("_bf16") else 7) for k in LIBRARY["sgemm_mx_out"]},  # dims, A, Bt, SAp, SBp, Y [, SY]
     **{k: 3 for k in LIBRARY["mx_quantize"]},  # X, codes, scales / dims, S, P
     **{k: 3 for k in LIBRARY["mx4_quantize"]},  # X, codes (two per byte), scales
     **{k: 3 for k in LIBRARY["mandelbrot"]},

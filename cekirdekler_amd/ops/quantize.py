@@ -28,6 +28,7 @@ from ..arrays import ClArray
 from ..cruncher import ClComputeError, ClNumberCruncher
 from .codecs import FP4_E2M1_EMAX, FP8_E4M3_EMAX, MX_BLOCK, from_bf16_bits, pack_fp4, to_mxfp4, to_mxfp8
 from .library import LIBRARY, library
+from .tiling import pack_mx_scales
 
 QUANTIZE_KERNELS = {"float32": "cek_mx_quantize_f32", "bfloat16": "cek_mx_quantize_bf16"}
 QUANTIZE4_KERNELS = {"float32": "cek_mx4_quantize_f32", "bfloat16": "cek_mx4_quantize_bf16"}
@@ -167,6 +168,46 @@ def mxfp4_kernel_model(x, src: str = "float32") -> tuple:
     codes = np.where(nan, np.uint32(0), w).astype(np.uint8).reshape(x.shape)
     sb = np.where(nan.any(axis=1), np.uint32(0xFF), sb)
     return pack_fp4(codes), sb.astype(np.uint8).reshape(x.shape[:-1] + (-1,))
+
+
+def relu_model(x: np.ndarray) -> np.ndarray:
+    """The GEMM epilogue's ReLU (``kernels/gemm8_out.h``) on float32 bit
+    patterns, in integer operations: ``x > 0`` and every NaN stay as they
+    are, everything else (``-0`` included) becomes ``+0``."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    keep = (u.view(np.int32) > 0) | ((u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000))
+    return np.where(keep, u, np.uint32(0)).view(np.float32)
+
+
+def bf16_bits_model(x: np.ndarray) -> np.ndarray:
+    """The epilogue's fp32 → bf16 on bit patterns: round to nearest even on
+    the integer, a NaN keeps its high half and gets the quiet bit."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    r = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, (u >> np.uint32(16)) | np.uint32(0x40), r).astype(np.uint16)
+
+
+def gemm_out_model(c: np.ndarray, out: str, act: str | None = None) -> tuple:
+    """The output-mode epilogue of the MX GEMMs (``kernels/gemm8_out.h``)
+    step by step on the fp32 ``[M][N]`` values the plain kernel would store:
+    the activation, then the conversion of ``out`` (``"bfloat16"``: the
+    integer rounding; ``"mxfp8"`` / ``"mxfp4"``: the quantise kernels' models,
+    blocks of 32 along N), then the pack of the scales.  Returns ``(Y, SY,
+    packed)``: bf16 bit patterns ``[M][N]`` with ``None, None``, or the codes
+    (``[M][N]``, MXFP4 ``[M][N/2]``), the scale bytes ``[M][N/32]`` and
+    :func:`~cekirdekler_amd.ops.tiling.pack_mx_scales` of them."""
+    c = np.ascontiguousarray(c, np.float32)
+    if act not in (None, "relu"):
+        raise ValueError(f"act must be None or 'relu' (got {act!r})")
+    if act == "relu":
+        c = relu_model(c)
+    if out == "bfloat16":
+        return bf16_bits_model(c), None, None
+    if out not in ("mxfp8", "mxfp4"):
+        raise ValueError(f"out must be 'bfloat16', 'mxfp8' or 'mxfp4' (got {out!r})")
+    codes, scales = (mxfp8_kernel_model if out == "mxfp8" else mxfp4_kernel_model)(c)
+    return codes, scales, pack_mx_scales(scales)
 
 
 _FLAGS = ("read", "partial_read", "write", "elements_per_work_item", "gather_resident")

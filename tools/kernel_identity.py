@@ -4,7 +4,8 @@
 Builds kernels/*.hip of both trees with build_native's command line and
 tools/microbench/gemm_loop.hip device-only in its three forms, unbundles the
 gfx950 ELF of each and compares bytes: per file ``identical`` or the kernels
-whose bytes differ.  Exit status 1 on any difference.  No instruction is
+whose bytes differ; a file REV does not have is reported as ``new``.  Exit
+status 1 on any difference.  No instruction is
 inspected.  Usage: python tools/kernel_identity.py REV
 """
 import concurrent.futures as cf, hashlib, io, os, shutil, struct, subprocess, sys, tarfile, tempfile
@@ -73,6 +74,9 @@ def main() -> int:
     bad = 0
     for name in sorted(set(old) | set(new)):
         a, b = old.get(name, b""), new.get(name, b"")
+        if name not in old:  # a file this tree adds: nothing to be identical to
+            print(f"{name}: new  sha256 {hashlib.sha256(b).hexdigest()}")
+            continue
         if a == b:
             print(f"{name}: identical  sha256 {hashlib.sha256(a).hexdigest()}")
             continue
