@@ -4,14 +4,21 @@ with and without ReLU.  Every comparison is exact: against the host codec of
 a float64-exact product (integers under mixed block scales), against the host
 codec of the plain kernel's C (wide-range data, NaN / Inf / zero rows), through
 a chain of two layers that shares the resident output as the next operand,
-and on two and three logical devices with every replica whole.
+on two and three logical devices with every replica whole, and against the
+host codec of designed fp32 accumulator bits that the GEMM itself is made to
+produce (gemm_out_oracles.py: ties, saturation, subnormals, denormals, single
+Inf elements and NaN columns; −0 and a NaN element on its own cannot be
+reached that way and stay with the host tier).
 
 Shapes: at least two tiles each way, M ≠ N (a transposed or mis-pitched store
-shows), K = 256 (one K-tile of MXFP4, two of MXFP8), one ragged tile group."""
+shows), K = 256 (one K-tile of MXFP4, two of MXFP8), one ragged tile group.
+The designed bits take two tile rows of one tile column at K = J·N, J the
+pieces per element (14 for MXFP8 operands, 27 or 28 for MXFP4 ones)."""
 import numpy as np
 import pytest
 
 import cekirdekler_amd as ck
+import gemm_out_oracles as goo
 from cekirdekler_amd.ops.gemm import (MX_OUTPUTS, GemmMxFp4, GemmMxFp8, pack_fp4, to_fp4_e2m1_codes,
                                       to_fp8_e4m3_bits, unpack_fp4)
 from cekirdekler_amd.ops.library import library
@@ -317,3 +324,63 @@ def test_logical_devices_hold_whole_outputs(cr, ndev, fmt, out):
         assert_same_output(_stored(g, download=False), want, out, "host-resident")
     finally:
         c.dispose()
+
+
+# ------------------------------------------ 6: designed fp32 accumulator bits
+
+_DESIGNED = {}
+
+
+def _designed_shape(fmt, tile):
+    M, N = goo.SHAPES[tile]
+    return M, N, goo.decompose_tile(tile, fmt)[4] * N
+
+
+def _set_designed(g, fmt, tile):
+    """The operands of gemm_out_oracles.decompose_tile through _set_ints,
+    encoded once per (format, tile)."""
+    key = ("operands", fmt, tile)
+    arrays = (g.A, g.B, g.SA, g.SB)
+    if key not in _DESIGNED:
+        _set_ints(g, *goo.decompose_tile(tile, fmt)[:4])
+        _DESIGNED[key] = tuple(x.array.copy() for x in arrays)
+    for dst, src in zip(arrays, _DESIGNED[key]):
+        dst.array[:] = src
+
+
+@pytest.mark.parametrize("tile", sorted(goo.SHAPES))
+@pytest.mark.parametrize("fmt", sorted(FORMATS))
+def test_plain_kernel_builds_the_designed_accumulators(cr, fmt, tile):
+    """The plain MX GEMM on accumulators that span fp32's whole range: every
+    finite and Inf element of gemm_out_oracles.gpu_target bit for bit, NaN
+    exactly in its NaN columns.  What the output-mode cases below convert is
+    therefore the designed bits."""
+    target = goo.gpu_target(tile)
+    c = _plain_c(FORMATS[fmt], _designed_shape(fmt, tile), tile, 4, cr, fill=lambda g: _set_designed(g, fmt, tile))
+    fin, inf, nan = goo.classes(target)
+    got_nan = goo.classes(c)[2]
+    bad = np.argwhere((got_nan != nan) | (~nan & (c.view(np.uint32) != target.view(np.uint32))))
+    assert bad.size == 0, (fmt, tile, len(bad), [(int(m), int(n), hex(int(target.view(np.uint32)[m, n])),
+                                                  hex(int(c.view(np.uint32)[m, n]))) for m, n in bad[:6]])
+    # the NaN the epilogue is handed carries a sign bit: the e4m3 NaN code has a sign to drop
+    assert (c.view(np.uint32)[nan] >> 31).any()
+    assert nan.sum() >= 2 * target.shape[0] and inf.sum() >= 32 and (np.abs(target[fin]) < 2.0 ** -126).sum() > 100
+
+
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("out", MX_OUTPUTS)
+@pytest.mark.parametrize("tile", sorted(goo.SHAPES))
+@pytest.mark.parametrize("fmt", sorted(FORMATS))
+def test_designed_accumulators_through_every_output(cr, fmt, tile, out, act):
+    """gemm8_out.h on designed bits: rounding ties ± 1 ulp of bf16, e4m3 and
+    e2m1, the carry to Inf, saturation, subnormal codes and fp32 denormals,
+    a single Inf or NaN element in a finite block (the NaN of a NaN column;
+    the two tiles' columns meet all four lanes of an MXFP4 block), negatives, denormals and
+    NaN under ReLU; every designed block in both bytes of a wave's scale
+    word (gemm_out_oracles.place)."""
+    target = goo.gpu_target(tile)
+    g = FORMATS[fmt](*_designed_shape(fmt, tile), cruncher=cr, tile=tile, group_m=4, fill="none", out=out, act=act)
+    _set_designed(g, fmt, tile)
+    got = _run_out(g)
+    assert_same_output(got, host_codec(target, out, act), out, (fmt, tile, out, act))
+    goo.assert_designed_cases_present(got, target, out, act)
