@@ -20,6 +20,16 @@ stage never bounces through host memory.  Slice ownership follows the
 balancer split of the stage's last kernel, snapshotted when the push that
 wrote the output ended.  Only pipeline inputs and results cross PCIe.
 
+A multi-device stage keeps its replicas coherent: after every kernel each
+device's slice of every output and of every hidden buffer not marked
+read_only is gathered into the other devices' replicas (keep-resident
+gather, device to device).  Hidden state therefore survives a moved split,
+a later kernel of the stage may read what an earlier one wrote at any index,
+and every replica of an output is whole whichever kernel wrote it.  The
+reference leaves this open ("todo: multi-gpu stage buffers will sync",
+ClPipeline.cs:267).  docs/API.md states the rules; tests/pipeline_model.py
+is their executable model.
+
 **Single-device multi-queue pipeline** (reference ``DevicePipeline`` /
 ``DevicePipelineStage`` / ``DevicePipelineArray(Type)``,
 ClPipeline.cs:2363-3234).  N stages on one device, each launched on its own
@@ -165,6 +175,8 @@ class ClPipelineStage:
     def _setup(self) -> None:
         if self.devices is None or len(self.devices) == 0:
             raise ValueError(f"stage {self.stage_id} has no devices")
+        if len(self.devices) > 1:
+            self._check_coverage()
         self.cruncher = ClNumberCruncher(self.devices, self.kernel_source, no_pipelining=True)
         if self.cruncher.error_code():
             raise RuntimeError(f"stage {self.stage_id} build failed:\n{self.cruncher.error_message()}")
@@ -176,6 +188,16 @@ class ClPipelineStage:
         self._out_dup = [_clone(a) for a in self.outputs]
         for a in self.inputs + self._in_dup + self.outputs + self._out_dup + self.hiddens:
             a.read, a.partial_read, a.write = False, False, False
+        if len(self._ordinals) > 1:
+            # Coherence on a multi-device stage: after every kernel each
+            # device's slice of every array a kernel may write (outputs, and
+            # hidden buffers not marked read_only) goes into every other
+            # device's replica, device to device (keep-resident gather).  A
+            # later kernel, or a later push after the balancer moved the
+            # split, then reads the same values on whichever device it runs.
+            for a in self.outputs + self._out_dup + self.hiddens:
+                if not a.read_only:
+                    a.gather_resident = True
         # materialise every replica with the host contents once (constants,
         # initial state); from here on nothing moves except by the pipeline
         for a in self.inputs + self._in_dup + self.outputs + self._out_dup + self.hiddens:
@@ -183,6 +205,32 @@ class ClPipelineStage:
                 self.cruncher.upload(a, d)
         self._owner = None      # (refs, ranges, local) of the output's writer
         self._owner_next = None
+
+    @staticmethod
+    def _covered(a: ClArray, global_range: int, local_range: int) -> int:
+        """Elements of ``a`` that the work items of one kernel own: the
+        devices' slices tile exactly these."""
+        if a.elements_per_group:
+            return (global_range // local_range) * a.elements_per_group
+        return global_range * a.elements_per_work_item
+
+    def _check_coverage(self) -> None:
+        """A multi-device stage keeps a written hidden buffer coherent by
+        gathering the devices' slices; elements past every kernel's
+        ``range · elements per work item`` belong to no slice, so state kept
+        there would differ from device to device."""
+        launches = list(zip(self.global_ranges, self.local_ranges)) + list(zip(self.init_globals, self.init_locals))
+        for j, a in enumerate(self.hiddens):
+            if a.read_only or not launches:
+                continue
+            cover = max(self._covered(a, G, L) for G, L in launches)
+            if a.N > cover:
+                raise ValueError(
+                    f"stage {self.stage_id}: hidden buffer {j} has {a.N} elements but the work items of the stage's "
+                    f"kernels own only {cover} (range x elements per work item); on a stage with "
+                    f"{len(self.devices)} devices the elements past that cannot be kept coherent. Mark the "
+                    f"buffer read_only if no kernel writes it, size it by its elements_per_work_item or "
+                    f"elements_per_group, or run the stage on one device")
 
     def _snapshot_owner(self) -> None:
         """Record which device computed which slice of this push's outputs
@@ -196,7 +244,10 @@ class ClPipelineStage:
     def _slices(self, a: ClArray):
         """(device, byte offset, bytes) of every device's slice of output
         ``a`` as last written; one whole-array slice from device 0 for a
-        single-device stage or before the first push."""
+        single-device stage or before the first push.  Elements past the
+        last work item's own (a tail no kernel writes) travel with device
+        0's replica, so that the whole array moves as it does from a
+        single-device stage."""
         if self._owner is None:
             return [(0, 0, a.nbytes)]
         refs, ranges, local = self._owner
@@ -211,6 +262,9 @@ class ClPipelineStage:
             c = max(0, min(c, a.nbytes - b))
             if c:
                 out.append((d, b, c))
+        end = self._covered(a, sum(ranges), local) * item
+        if end < a.nbytes:
+            out.append((0, end, a.nbytes - end))
         return out
 
     def _group(self, dup: bool) -> ClParameterGroup:
@@ -278,6 +332,8 @@ class ClPipeline:
         self.counter = 0
         self._pool = ThreadPoolExecutor(max_workers=max(1, len(stages)))
         self.engine = cek.CopyEngine()
+        self._sources: List[ClArray] = []  # wrappers of this push's data, alive until the copies are done
+        self._wrapped: list = []           # (result, wrapper) of this push's results that were wrapped
 
     def _forward(self, data, results) -> None:
         """Enqueue every transfer of this push (no host sync): host data into
@@ -285,10 +341,16 @@ class ClPipeline:
         stage's spare inputs, the last stage's previous outputs to the host."""
         e = self.engine
         last = len(self.stages) - 1
+        # a list, a strided view or a tensor is copied into a temporary ClArray:
+        # it must outlive the asynchronous copies that read it (push_data
+        # drops these after the engine's sync)
+        self._sources = []
         if data is not None:
             st = self.stages[0]
             for dst, d in zip(st._in_dup, data):
-                _transfer(e, st, dst, None, as_clarray(d))
+                w = as_clarray(d)
+                self._sources.append(w)
+                _transfer(e, st, dst, None, w)
         for k in range(last):
             st, nxt = self.stages[k], self.stages[k + 1]
             for dst, src in zip(nxt._in_dup, st._out_dup):
@@ -324,6 +386,7 @@ class ClPipeline:
         finally:
             for f in futs:
                 f.result()
+        self._sources = []  # the copies that read them are complete
         for r, w in self._wrapped:  # a non-contiguous result was wrapped through a copy
             view = np.asarray(r)
             if not np.shares_memory(view, w.array):
