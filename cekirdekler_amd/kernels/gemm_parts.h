@@ -50,7 +50,15 @@ __device__ __forceinline__ unsigned cek_stage_lane_off(int lane, int K) {
 // and lands at lds + (w·PER + j) KiB.
 // The operands come by reference on purpose: as in a lambda that captures by
 // reference, the compiler then sees them as loop-invariant only after the
-// loop is unrolled, and keeps the wave-uniform base + per-lane offset form.
+// loop is unrolled.  What it emits (gfx950, -O3): the saddr form
+// (global_load_lds_dwordx4 vOFF, s[BASE:BASE+1]) only where the lane offset's
+// zero-extension sits in the block of the load, which is the prologues and
+// some MODE 0 / 2 loops; inside the ping-pong K loops the zero-extension is
+// hoisted out, and every load takes a 64-bit VGPR address made by one
+// v_lshl_add_u64 (uniform base + extended offset) in front of it.  The flat
+// loops of sgemm_bf16.hip (FLAT 2) form the offset again inside the loop and
+// get the saddr form there; the byte-identity of the other kernels is why
+// this helper is left as it is.
 template <int N, int ESZ, int PER = N>
 __device__ __forceinline__ void cek_stage_rows(const char* const& rows, const unsigned& lane_off, const int& K,
                                                const int& ks, const int& kt, char* lds, const int& w, int j0 = 0) {

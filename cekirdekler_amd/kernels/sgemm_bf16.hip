@@ -22,12 +22,29 @@
 // 16-B chunk index is XOR-swizzled with (row & 7) on the global SOURCE
 // address and on the ds_read_b128 address (rule 21), which makes every
 // fragment read conflict-free (each 16-lane group hits 16 distinct slots).
+//
+// The ping-pong kernels (MODE 2 / 4 / 6) split the work-group into two wave
+// groups that alternate between a read section and an MFMA section.  Their K
+// loop is written once for both groups; the two full-problem kernels
+// (256x256pb, 256x256pbr) instead run one branch-free loop per group with the
+// LDS-DMA addresses in SGPR base + 32-bit lane offset form (FLAT 2 of
+// gemm_tile; profiles/gemm_flat_loop.md: the read section is the critical
+// path, and it got about 200 cycles per K-tile shorter).  256x256pb0 keeps
+// the shared loop as their reference tile: same C to the bit.
 #include "gemm_parts.h"
 
 // Per-work-group timeline stamps (tools/microbench/gemm_loop.hip defines it
 // in its timeline build; empty in the library).
 #ifndef CEK_TS
 #define CEK_TS(k)
+#endif
+// Section stamps of one mid-loop K-tile of the MODE 4 ping-pong (the same
+// timeline build): CEK_SEC(p, kt) at the five points of an iteration,
+// CEK_SEC_DECL before the loop, CEK_SEC_FLUSH after it.  Empty in the library.
+#ifndef CEK_SEC
+#define CEK_SEC_DECL
+#define CEK_SEC(p, kt)
+#define CEK_SEC_FLUSH
 #endif
 
 namespace {
@@ -39,17 +56,27 @@ constexpr int gemm_lds_bytes(int WM, int WN, int FM, int FN, int MODE) {
   return MODE == 4 ? 2 * a + 3 * b : MODE == 6 ? 3 * (a + b) : 2 * (a + b);
 }
 
+// A compile-time count handed to a generic lambda.
+template <int V>
+struct cek_count {
+  constexpr int operator()() const { return V; }
+};
+
 // The parts below are lambdas that capture by reference, and the shared
 // helpers take their operands by reference: written so, the device code is
 // byte-identical to the one-function-per-variant text this replaced
 // (tools/kernel_identity.py).
-template <int WM, int WN, int FM, int FN, int MODE, bool SK = false, int XCH = 0, bool ROWC = false>
+// FLAT (MODE 4 only): 0 the K loop written once for both ping-pong groups,
+// 1 one branch-free K loop per group (below, "flat loops"), 2 the same with
+// the LDS-DMA source formed as wave-uniform base + 32-bit lane offset.
+template <int WM, int WN, int FM, int FN, int MODE, bool SK = false, int XCH = 0, bool ROWC = false, int FLAT = 0>
 __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
                                           const uint16_t* __restrict__ A,
                                           const uint16_t* __restrict__ Bt, float* __restrict__ C,
                                           char* smem, long long off, float* __restrict__ W = nullptr,
                                           int* __restrict__ tile_cnt = nullptr) {
   static_assert(MODE == 0 || MODE == 2 || MODE == 4 || MODE == 6, "MODE is 0, 2, 4 or 6");
+  static_assert(FLAT == 0 || MODE == 4, "the flat loops are MODE 4's");
   constexpr int BM = WM * 16 * FM, BN = WN * 16 * FN, BK = 64;
   constexpr int NREG = WM * WN;
   constexpr int NWAVES = NREG, NT = 64 * NWAVES;
@@ -130,6 +157,20 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
       __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + lane_off), (lds_void*)(base + (sw * B_INSTR + j) * 1024),
                                        16, 0, 0);
     }
+  };
+
+  // The flat loops' issue sequence: N blocks of K-tile kt from `rows` into
+  // the buffer at `lds`.  FLAT 2 hides the lane offset's origin from the
+  // compiler here, once per K-tile, so that its zero-extension is formed next
+  // to the loads and each address is an SGPR pair + a 32-bit VGPR offset.
+  auto stage_flat = [&](auto n, const char* rows, char* lds, int kt) __attribute__((always_inline)) {
+    unsigned lo = lane_off;
+    if constexpr (FLAT == 2) asm volatile("" : "+v"(lo));
+    const char* src = rows + (size_t)CEK_KTILE(ks, kt) * BK * 2;
+#pragma unroll
+    for (int j = 0; j < n(); ++j)
+      __builtin_amdgcn_global_load_lds((glb_cvoid*)(src + (size_t)j * 8 * K * 2 + lo),
+                                       (lds_void*)(lds + (sw * n() + j) * 1024), 16, 0, 0);
   };
 
   // ---- fragments, MFMA section, barrier ----
@@ -285,6 +326,80 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
   };
   if constexpr (MODE == 0) {
     single_stage_loop();
+  } else if constexpr (FLAT != 0) {
+    // Flat loops (MODE 4): the ping-pong below with one K loop per group,
+    // chosen once.  Barriers, waits, staging targets and the MFMA order per
+    // accumulator are the shared loop's, so C is the same to the bit; what
+    // goes is the per-iteration re-testing of g1, kt + 1 < nk, kt + 2 < nk
+    // and the kt % 3 arithmetic inside the read section.  The buffers of
+    // K-tile kt are carried as LDS byte offsets (scalars, stepped once per
+    // iteration): a_rd = (kt & 1)·A_BYTES, b_rd = (kt % 3)·B_BYTES; G1's
+    // target for K-tile kt + 2 is the Bt buffer of kt − 1.  The last K-tiles
+    // (nothing left to stage) run in a loop of their own, so the steady-state
+    // body has no branch but its back edge.
+    if (!g1) {
+      stage_g0(0);
+    } else {
+      stage_g1(0);
+      if (nk > 1) stage_g1(1);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    bar();
+    CEK_TS(1);
+    CEK_SEC_DECL;
+    int a_rd = 0, b_rd = 0, kt = 0;
+    auto step = [&] {
+      a_rd ^= A_BYTES;
+      b_rd = b_rd == 2 * B_BYTES ? 0 : b_rd + B_BYTES;
+    };
+    auto reads = [&]() __attribute__((always_inline)) {
+      ldall(a_base + a_rd, b_base + b_rd - A_BYTES);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
+    if (!g1) {
+      auto tile = [&](auto staging) __attribute__((always_inline)) {
+        CEK_SEC(0, kt);
+        if constexpr (staging() != 0) stage_flat(cek_count<A_INSTR>{}, a_wave, a_base + (a_rd ^ A_BYTES), kt + 1);
+        reads();
+        CEK_SEC(1, kt);
+        bar();
+        CEK_SEC(2, kt);
+        mmaall();
+        CEK_SEC(3, kt);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        bar();
+        CEK_SEC(4, kt);
+        step();
+      };
+      for (; kt + 1 < nk; ++kt) tile(cek_count<1>{});
+      for (; kt < nk; ++kt) tile(cek_count<0>{});
+      bar();  // equal barrier counts for both groups
+    } else {
+      bar();  // G1 runs one section behind
+      int b_st = 2 * B_BYTES;  // where K-tile kt + 2 goes
+      auto tile = [&](auto staging) __attribute__((always_inline)) {
+        CEK_SEC(0, kt);
+        if constexpr (staging() != 0) stage_flat(cek_count<B_INSTR>{}, b_wave, b_base + b_st, kt + 2);
+        reads();
+        if constexpr (staging() != 0)
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G1_AHEAD) : "memory");
+        else
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        CEK_SEC(1, kt);
+        bar();
+        CEK_SEC(2, kt);
+        mmaall();
+        CEK_SEC(3, kt);
+        bar();
+        CEK_SEC(4, kt);
+        b_st = b_rd;
+        step();
+      };
+      for (; kt + 2 < nk; ++kt) tile(cek_count<1>{});
+      for (; kt < nk; ++kt) tile(cek_count<0>{});
+    }
+    CEK_SEC_FLUSH;
+    CEK_TS(2);
   } else {
     if (!g1) {
       stage_g0(0);
@@ -295,8 +410,10 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bar();
     if constexpr (MODE == 4) CEK_TS(1);  // the timeline build stamps the production loop only
+    CEK_SEC_DECL;
     if (g1) bar();  // G1 runs one section behind
     for (int kt = 0; kt < nk; ++kt) {
+      if constexpr (MODE == 4) CEK_SEC(0, kt);
       // MODE 2 takes its stage's address ahead of the staging, MODE 4 and 6
       // after it: the order the variants always had, kept for identical code
       const char* pp_base = smem + (kt & 1) * STAGE;
@@ -318,12 +435,17 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
       }
+      if constexpr (MODE == 4) CEK_SEC(1, kt);
       bar();
+      if constexpr (MODE == 4) CEK_SEC(2, kt);
       mmaall();
+      if constexpr (MODE == 4) CEK_SEC(3, kt);
       if (!g1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       bar();
+      if constexpr (MODE == 4) CEK_SEC(4, kt);
     }
     if (!g1) bar();  // equal barrier counts for both groups
+    if constexpr (MODE == 4) CEK_SEC_FLUSH;
     if constexpr (MODE == 4) CEK_TS(2);
   }
   // Epilogue: acc[i][j][r] is C(row = wr·16FM + i·16 + fq·4 + r, col = wc·16FN + j·16 + fr)
@@ -648,42 +770,50 @@ __device__ __forceinline__ void gemm_tile(const int* __restrict__ dims,
 #define CEK_WS_PARAMS_1 float *W, int *tile_cnt,
 #define CEK_WS_ARGS_0
 #define CEK_WS_ARGS_1 , W, tile_cnt
-#define CEK_GEMM_KERNEL(NAME, WM, WN, FM, FN, MODE, SK, XCH, ROWC)                                          \
+#define CEK_GEMM_KERNEL(NAME, WM, WN, FM, FN, MODE, SK, XCH, ROWC, FLAT)                                    \
   extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                           \
       const int* dims, const uint16_t* A, const uint16_t* Bt, float* C, CEK_WS_PARAMS_##SK CEK_HIDDEN) {      \
     __shared__ __attribute__((aligned(16))) char smem[gemm_lds_bytes(WM, WN, FM, FN, MODE)];                  \
-    gemm_tile<WM, WN, FM, FN, MODE, SK, XCH, ROWC>(dims, A, Bt, C, smem, __cek_off CEK_WS_ARGS_##SK);         \
+    gemm_tile<WM, WN, FM, FN, MODE, SK, XCH, ROWC, FLAT>(dims, A, Bt, C, smem, __cek_off CEK_WS_ARGS_##SK);   \
   }
 
 // Split-K ping-pong variants (dims[4] = S splits; K/64 divisible by S):
 // strongly scaled slices keep one 256-row tile per CU busy instead of
 // leaving CUs idle (8 GPUs × 1024 rows of an 8192² problem = 128 tiles).
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pp_sk, 2, 4, 8, 4, 2, 1, 0, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pp_sk, 2, 4, 8, 4, 2, 1, 0, 0, 0)
 // balanced-DMA split-K (three Bt buffers: 160 KiB LDS)
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sk, 2, 4, 8, 4, 4, 1, 0, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sk, 2, 4, 8, 4, 4, 1, 0, 0, 0)
 // uneven split-K = 2 with a one-way hand-over (dims[5] = the helper's
 // K-tile deficit): the helper's partial stores overlap the owner's last
 // K-tiles instead of both sides' exchange landing at the end of the launch
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sw, 2, 4, 8, 4, 4, 1, 3, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sw, 2, 4, 8, 4, 4, 1, 3, 0, 0)
 // the same with the row halves exchanged at the end (XCH 4): the owner's
 // tail carries 384 KiB instead of 512, the helper stores half of C
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sh, 2, 4, 8, 4, 4, 1, 4, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_sh, 2, 4, 8, 4, 4, 1, 4, 0, 0)
 // halves exchanged with both partial stores in flight at once (XCH 5):
 // meant for an even split (dims[5] = 0), both sides ending together
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_ss, 2, 4, 8, 4, 4, 1, 5, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb_ss, 2, 4, 8, 4, 4, 1, 5, 0, 0)
 
 // Balanced-DMA ping-pong (MODE 4):
-// 160 KiB LDS at 256², 128 KiB at 256×128.
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb, 2, 4, 8, 4, 4, 0, 0, 0)
+// 160 KiB LDS at 256², 128 KiB at 256×128.  The two full-problem kernels run
+// the flat loops (FLAT 2); the others keep the shared loop.
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb, 2, 4, 8, 4, 4, 0, 0, 0, 2)
+// its reference tile: the shared loop (what 256x256pb was before the flat loops)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb0, 2, 4, 8, 4, 4, 0, 0, 0, 0)
+#ifdef CEK_PROBE_KERNELS
+// tools/microbench/gemm_loop.hip only: the flat loops with the staging
+// addresses left as the compiler forms them (FLAT 1)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pb1, 2, 4, 8, 4, 4, 0, 0, 0, 1)
+#endif
 // the same with C row-major ([M][N]) through an LDS turn-around per wave
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pbr, 2, 4, 8, 4, 4, 0, 0, 1)
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x128pb, 4, 2, 4, 4, 4, 0, 0, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pbr, 2, 4, 8, 4, 4, 0, 0, 1, 2)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x128pb, 4, 2, 4, 4, 4, 0, 0, 0, 0)
 
 // Even chunk-split DMA with three whole stages (MODE 6): 144 KiB at 256×128.
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x128pe, 4, 2, 4, 4, 6, 0, 0, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x128pe, 4, 2, 4, 4, 6, 0, 0, 0, 0)
 
 // 256×256 tiles, 8 waves (2×4, 128×64 each), 128 KiB LDS, 1 block/CU.
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256, 2, 4, 8, 4, 0, 0, 0, 0)
-CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pp, 2, 4, 8, 4, 2, 0, 0, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256, 2, 4, 8, 4, 0, 0, 0, 0, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_256x256pp, 2, 4, 8, 4, 2, 0, 0, 0, 0)
 // 128×128 tiles, 4 waves (2×2, 64×64 each), 64 KiB LDS, 2 blocks/CU.
-CEK_GEMM_KERNEL(cek_sgemm_bf16_128x128, 2, 2, 4, 4, 0, 0, 0, 0)
+CEK_GEMM_KERNEL(cek_sgemm_bf16_128x128, 2, 2, 4, 4, 0, 0, 0, 0, 0)

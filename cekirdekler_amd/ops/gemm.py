@@ -38,7 +38,9 @@ from .tiling import pack_mx_scales, rows_to_tile, tile_coords, tile_to_rows, unp
 # in rounds 1-2 is in git history, with its numbers in profiles/gemm_*.md.
 TILES = {
     # balanced-DMA ping-pong (G0 stages A, G1 stages Bt two K-tiles ahead):
-    # the full-problem tile (1.47-1.50 PF at 8192³)
+    # the full-problem tile, one branch-free K loop per wave group (1.55-1.57 PF
+    # at 8192³ where its reference tile 256x256pb0 runs 1.51;
+    # profiles/gemm_flat_loop.md)
     "256x256pb": (256, 256, 512, "cek_sgemm_bf16_256x256pb"),
     # the same kernel with C row-major [M][N] (an LDS turn-around per wave in
     # the epilogue): the layout hipBLASLt writes, for like-for-like numbers;
@@ -70,6 +72,15 @@ TILES = {
     # small problems: 2 blocks per CU
     "128x128": (128, 128, 256, "cek_sgemm_bf16_128x128"),
 }
+
+# Reference tiles: kernels kept to measure and check a production tile
+# against, accepted by GemmBf16(tile=...) like the tiles above but not part of
+# the tile set.  256x256pb0 is 256x256pb with the K loop written once for
+# both wave groups (the loop 256x256pb had before its flat loops): C is the
+# same to the bit (tests/test_gpu_gemm_flat_loop.py), and tools/scale_probe.py
+# and tools/microbench/gemm_loop measure against it.
+REFERENCE_TILES = {"256x256pb0": (256, 256, 512, "cek_sgemm_bf16_256x256pb0")}
+REFERENCE_TILE_WAVES = {"256x256pb0": (2, 4, 8, 4)}
 
 GEMM_LIBS = ("sgemm_bf16",)
 
@@ -212,13 +223,14 @@ class GemmBf16:
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
                  group_m: int = 4, split_k: int = 1, wave_granularity: bool | None = None,
                  exchange_shift: int | None = None, handover_spin_limit: int = 0):
-        BM, BN, L, kname = self.TILE_TABLE[tile]
+        # split-K, exchange, row-major C and reference tiles are variants of the bf16 tiles alone
+        bf16 = self.TILE_TABLE is TILES
+        reference = bf16 and tile in REFERENCE_TILES
+        BM, BN, L, kname = REFERENCE_TILES[tile] if reference else self.TILE_TABLE[tile]
         self.tile = tile
         if M % BM or N % BN or K % self.K_MULTIPLE or (self.POSITIVE_DIMS and min(M, N, K) <= 0):
             raise ValueError(f"M%{BM}, N%{BN} and K%{self.K_MULTIPLE} must be 0"
                              + (" and M, N, K positive" if self.POSITIVE_DIMS else "") + f" (got {M},{N},{K})")
-        # split-K, exchange and row-major C are variants of the bf16 tiles alone
-        bf16 = self.TILE_TABLE is TILES
         if split_k > 1:
             if tile not in SPLIT_K_TILES:
                 raise ValueError(f"split-K is available for tiles {sorted(SPLIT_K_TILES)}")
@@ -236,7 +248,7 @@ class GemmBf16:
                 shift = max(0, min(shift, K // 128 - 1))  # the helper keeps >= 1 K-tile
         self.exchange_shift = shift
         self.M, self.N, self.K, self.BM, self.BN, self.L, self.kernel = M, N, K, BM, BN, L, kname
-        self.geom = self.TILE_GEOM[tile] if self.TILE_GEOM else None
+        self.geom = REFERENCE_TILE_WAVES[tile] if reference else self.TILE_GEOM[tile] if self.TILE_GEOM else None
         self.row_major_c = bf16 and tile in ROW_MAJOR_TILES
         self.split_k = max(1, int(split_k))
         self.tiles = (M // BM) * (N // BN)

@@ -6,7 +6,15 @@ tools/microbench/gemm_loop.hip device-only in its three forms, unbundles the
 gfx950 ELF of each and compares bytes: per file ``identical`` or the kernels
 whose bytes differ; a file REV does not have is reported as ``new``.  Exit
 status 1 on any difference.  No instruction is
-inspected.  Usage: python tools/kernel_identity.py REV
+inspected.  Usage: python tools/kernel_identity.py REV [NEW=OLD ...]
+
+A kernel that grows, arrives or leaves moves the kernels after it, and a
+kernel descriptor (``NAME.kd``) holds the distance to its code: the per-kernel
+comparison leaves those eight bytes out, so a kernel is listed only when its
+code or the rest of its descriptor changed.  ``NEW=OLD`` compares this tree's
+kernel NEW (code and descriptor) with REV's kernel OLD, in every file that has
+both: ``256x256pb0=256x256pb`` shows that a reference tile is the kernel REV
+shipped under the other name.
 """
 import concurrent.futures as cf, hashlib, io, os, shutil, struct, subprocess, sys, tarfile, tempfile
 
@@ -62,8 +70,14 @@ def symbols(elf: bytes) -> dict:
     return out
 
 
+def placed(sym: dict) -> dict:
+    """The symbols with every descriptor's offset to its code (bytes 16-23 of the 64) zeroed."""
+    return {k: v[:16] + bytes(8) + v[24:] if k.endswith(".kd") and len(v) == 64 else v for k, v in sym.items()}
+
+
 def main() -> int:
     rev = sys.argv[1]
+    pairs = [a.split("=") for a in sys.argv[2:]]
     with tempfile.TemporaryDirectory() as tmp:
         tar = subprocess.run(["git", "-C", ROOT, "archive", rev, KREL, MREL], check=True, stdout=subprocess.PIPE).stdout
         tarfile.open(fileobj=io.BytesIO(tar)).extractall(os.path.join(tmp, "rev"))
@@ -82,9 +96,15 @@ def main() -> int:
             continue
         sha = " -> ".join(hashlib.sha256(x).hexdigest()[:16] for x in (a, b))
         bad += 1
-        sa, sb = (symbols(x) if x else {} for x in (a, b))
+        sa, sb = (placed(symbols(x)) if x else {} for x in (a, b))
         diff = sorted(k for k in set(sa) | set(sb) if sa.get(k) != sb.get(k))
         print(f"{name}: DIFFERENT  sha256 {sha}\n  " + ("\n  ".join(diff) or "(outside every sized symbol)"))
+        for new_k, old_k in pairs:
+            hit = [s for s in sb if s.endswith("_" + new_k) and s[:-len(new_k)] + old_k in sa]
+            for s in hit:
+                o = s[:-len(new_k)] + old_k
+                same = sb[s] == sa[o] and sb[s + ".kd"] == sa[o + ".kd"]
+                print(f"  {s}: {'identical to' if same else 'DIFFERENT from'} {rev}'s {o}")
     return 1 if bad else 0
 
 

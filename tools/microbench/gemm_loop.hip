@@ -8,6 +8,11 @@
 //                  tile (the operand stream hits L2), same instruction stream
 // The difference between the two is what operand latency/bandwidth costs the
 // ping-pong schedule.
+// Every build also times the 8192³ kernel's three K loops in interleaved
+// rounds: 256x256pb0 (the loop shared by both wave groups), 256x256pb1 (one
+// flat loop per group; built here only) and 256x256pb (flat loops with the
+// staging addresses as SGPR base + 32-bit lane offset, as shipped).
+#define CEK_PROBE_KERNELS
 #ifdef CEK_PROBE_L2
 #define CEK_KTILE(ks, kt) ((ks) + ((kt) & 1))
 #endif
@@ -30,6 +35,28 @@ __device__ __forceinline__ void cek_stamp(int k) {
   }
 }
 #define CEK_TS(k) cek_stamp(k)
+// Section stamps: at K-tile nk / 2 of a MODE 4 loop, wave 0 (group G0) and
+// wave NWAVES / 2 (G1) read s_memtime into SGPRs at (0) read-section start,
+// (1) before the first barrier, (2) after it, (3) after the last MFMA, (4)
+// after the second barrier; lane 0 stores the five after the loop, so the
+// stamped iteration carries no extra vector memory traffic.
+__device__ unsigned long long cek_sec[4096 * 16];
+#define CEK_SEC_DECL                                  \
+  unsigned long long cek_sec_t[5] = {0, 0, 0, 0, 0}; \
+  const bool cek_sec_on = wave == 0 || wave == NWAVES / 2
+#define CEK_SEC(p, kt)                               \
+  do {                                               \
+    if (cek_sec_on && (kt) == (nk >> 1)) {           \
+      __builtin_amdgcn_sched_barrier(0);             \
+      cek_sec_t[p] = __builtin_amdgcn_s_memtime();   \
+      __builtin_amdgcn_sched_barrier(0);             \
+    }                                                \
+  } while (0)
+#define CEK_SEC_FLUSH                                                                              \
+  do {                                                                                             \
+    if (cek_sec_on && lane == 0)                                                                   \
+      for (int p_ = 0; p_ < 5; ++p_) cek_sec[(blockIdx.x * 2 + (wave != 0)) * 8 + p_] = cek_sec_t[p_]; \
+  } while (0)
 #define CEK_TS_END                                \
   do {                                            \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
@@ -76,6 +103,16 @@ static const int N = 8192, SLICE = 1024;
 
 static void launch_full(hipStream_t s) {
   hipLaunchKernelGGL(cek_sgemm_bf16_256x256pb, dim3((N / 256) * (N / 256)), dim3(512), 0, s, g_dims, g_A, g_B, g_C,
+                     0LL, (long long)(N / 256) * (N / 256) * 512);
+}
+
+static void launch_full0(hipStream_t s) {
+  hipLaunchKernelGGL(cek_sgemm_bf16_256x256pb0, dim3((N / 256) * (N / 256)), dim3(512), 0, s, g_dims, g_A, g_B, g_C,
+                     0LL, (long long)(N / 256) * (N / 256) * 512);
+}
+
+static void launch_full1(hipStream_t s) {
+  hipLaunchKernelGGL(cek_sgemm_bf16_256x256pb1, dim3((N / 256) * (N / 256)), dim3(512), 0, s, g_dims, g_A, g_B, g_C,
                      0LL, (long long)(N / 256) * (N / 256) * 512);
 }
 
@@ -154,6 +191,33 @@ static void timeline(const char* name, void (*launch)(hipStream_t), int grid) {
   }
   printf("}\n");
 }
+
+// one launch, then the section stamps of its mid-loop K-tile: medians over
+// work-groups, in shader cycles, per wave group.  read = read section (DMA
+// issue, fragment reads, waits), wait1 = its barrier, mfma = MFMA section,
+// wait2 = the closing barrier (G0: with its vmcnt(0)), iter = the whole K-tile.
+static void sections(const char* name, void (*launch)(hipStream_t), int grid) {
+  std::vector<unsigned long long> sec((size_t)grid * 16, 0);
+  CK(hipMemcpyToSymbol(HIP_SYMBOL(cek_sec), sec.data(), sec.size() * 8));
+  launch(0);
+  CK(hipDeviceSynchronize());
+  CK(hipMemcpyFromSymbol(sec.data(), HIP_SYMBOL(cek_sec), sec.size() * 8));
+  printf("{\"sections\": \"%s\"", name);
+  const char* part[5] = {"read", "wait1", "mfma", "wait2", "iter"};
+  for (int g = 0; g < 2; ++g) {
+    std::vector<double> v[5];
+    for (int b = 0; b < grid; ++b) {
+      const unsigned long long* t = &sec[((size_t)b * 2 + g) * 8];
+      if (!t[0] || !t[4]) continue;
+      for (int p = 0; p < 4; ++p) v[p].push_back((double)(t[p + 1] - t[p]));
+      v[4].push_back((double)(t[4] - t[0]));
+    }
+    printf(", \"g%d\": {\"wgs\": %zu", g, v[0].size());
+    for (int p = 0; p < 5; ++p) printf(", \"%s\": [%.0f, %.0f, %.0f]", part[p], pct(v[p], 0.1), pct(v[p], 0.5), pct(v[p], 0.9));
+    printf("}");
+  }
+  printf("}\n");
+}
 #endif
 
 int main(int argc, char** argv) {
@@ -197,7 +261,20 @@ int main(int argc, char** argv) {
     printf("{\"variant\": \"%s\", \"kernel\": \"%s\", \"shift\": %d, \"shape\": \"1024x8192x8192\", \"ms\": %.4f, \"tflops\": %.1f}\n",
            variant, slice_name, shift, ms, 2.0 * SLICE * N * (double)N / ms / 1e9);
   }
+  // the three K loops, interleaved: argv[4] rounds (default 3) of `reps` launches each
+  const int ab_rounds = argc > 4 ? atoi(argv[4]) : 3;
+  struct {
+    const char* name;
+    void (*launch)(hipStream_t);
+  } loops[3] = {{"256x256pb0", launch_full0}, {"256x256pb1", launch_full1}, {"256x256pb", launch_full}};
+  for (int round = 0; round < ab_rounds; ++round)
+    for (auto& l : loops) {
+      const float ms = time_kernel(l.launch, reps);
+      printf("{\"variant\": \"%s\", \"loop_ab\": \"%s\", \"round\": %d, \"ms\": %.4f, \"tflops\": %.1f}\n", variant, l.name,
+             round, ms, 2.0 * N * N * (double)N / ms / 1e9);
+    }
 #ifdef CEK_PROBE_TS
+  for (auto& l : loops) sections(l.name, l.launch, (N / 256) * (N / 256));
   timeline("256x256pb 8192^3", launch_full, (N / 256) * (N / 256));
   char tl[64];
   snprintf(tl, sizeof tl, "%s 1024x8192x8192", slice_name);
