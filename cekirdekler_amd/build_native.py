@@ -27,7 +27,8 @@ BUILD = os.path.join(HERE, "_build")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("CEK_ARCH", "gfx950")
 
-SOURCES = ["device.cpp", "jit.cpp", "memory.cpp", "balancer.cpp", "worker.cpp", "dist.cpp",
+SOURCES = ["device.cpp", "jit.cpp", "memory.cpp", "balancer.cpp", "cpu_pool.cpp", "lanes.cpp", "replicas.cpp",
+           "markers.cpp", "kernel_stamps.cpp", "job_thread.cpp", "worker.cpp", "dist.cpp",
            "cores.cpp", "cores_run.cpp", "spans.cpp", "peer.cpp", "graphs.cpp", "downloads.cpp", "pool.cpp",
            "copy_engine.cpp", "shell_gemm.cpp", "xgmi.cpp", "probe.cpp", "refloops.cpp", "bindings.cpp"]
 

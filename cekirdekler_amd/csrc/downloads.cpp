@@ -32,7 +32,7 @@ void DeferredDownloads::flush(Worker& wk, hipStream_t next, const ComputeCall* c
     auto& ev = order_events_[w];
     while (ev.size() < order.size()) {
       ev.emplace_back();
-      ev.back().get(wk);
+      ev.back().get(wk.dev());
     }
     for (size_t i = 0; i < order.size(); ++i) {
       CEK_HIP(hipEventRecord(ev[i].peek(), order[i]));

@@ -11,6 +11,7 @@
 // order a flushed download against the next compute.
 #pragma once
 #include "events.h"
+#include "worker.h"
 
 namespace cek {
 

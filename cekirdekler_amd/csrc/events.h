@@ -1,14 +1,11 @@
-// An owning HIP event, created on first use: the scheduler's parts need most
-// of their events only on some paths, a CPU-only cruncher must not touch HIP
-// for them, and a stream capture must see no creation it did not see before.
+// An owning HIP event, created on first use: the worker's and the scheduler's
+// parts need most of their events only on some paths, a CPU-only cruncher must
+// not touch HIP for them, and a stream capture must see no creation it did not
+// see before.
 #pragma once
-#include "worker.h"
+#include "device.h"
 
 namespace cek {
-
-// The scheduler's workers as its parts see them: each part is given a
-// reference at construction and is destroyed before them.
-using Workers = std::vector<std::unique_ptr<Worker>>;
 
 class Event {
  public:
@@ -30,12 +27,12 @@ class Event {
     if (prev >= 0 && prev != ordinal_) (void)hipSetDevice(prev);
   }
 
-  // The event; the first call creates it with `flags` on wk's device.
-  hipEvent_t get(const Worker& wk, unsigned flags = hipEventDisableTiming) {
+  // The event; the first call creates it with `flags` on GPU `dev`.
+  hipEvent_t get(const DeviceInfo& dev, unsigned flags = hipEventDisableTiming) {
     if (!e_) {
-      wk.set_device();
+      CEK_HIP(hipSetDevice(dev.ordinal));
       CEK_HIP(hipEventCreateWithFlags(&e_, flags));
-      ordinal_ = wk.dev().ordinal;
+      ordinal_ = dev.ordinal;
     }
     return e_;
   }

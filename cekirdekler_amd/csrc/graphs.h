@@ -16,6 +16,7 @@
 #include <map>
 
 #include "events.h"
+#include "worker.h"
 
 namespace cek {
 

@@ -158,7 +158,7 @@ uint64_t PeerTraffic::issue_gather(const ComputeCall& c, const BalancerState& st
         }
       }
     }
-    CEK_HIP(hipEventRecord(pushed_[g].get(wg), m));
+    CEK_HIP(hipEventRecord(pushed_[g].get(wg.dev()), m));
   }
   gather_pending = true;
   if (!v.enqueue_mode) {
@@ -186,7 +186,7 @@ void PeerTraffic::copy_between(int src_dev, const ArraySpec& src, int dst_dev, c
     wd.set_device();
     void* dp = wd.buffer(dst);
     wd.join_streams(wd.main_stream());
-    hipEvent_t before = kdone_[dst_dev].get(wd);
+    hipEvent_t before = kdone_[dst_dev].get(wd.dev());
     CEK_HIP(hipEventRecord(before, wd.main_stream()));
     ws.set_device();
     hipStream_t s = ws.main_stream();
@@ -195,7 +195,7 @@ void PeerTraffic::copy_between(int src_dev, const ArraySpec& src, int dst_dev, c
     CEK_HIP(hipStreamWaitEvent(s, before, 0));
     d2d = D2DCount();
     d2d_copy(src_dev, dst_dev, static_cast<char*>(dp), static_cast<const char*>(sp), bytes, s, src_dev);
-    hipEvent_t after = pushed_[src_dev].get(ws);
+    hipEvent_t after = pushed_[src_dev].get(ws.dev());
     CEK_HIP(hipEventRecord(after, s));
     wd.set_device();
     CEK_HIP(hipStreamWaitEvent(wd.main_stream(), after, 0));
@@ -228,7 +228,7 @@ void PeerTraffic::share_slices(const BalancerState& st, const ArraySpec& a, long
     if (!wk.gpu() || !v.enabled[w]) continue;
     wk.set_device();
     wait_gather(wk, wk.main_stream());
-    CEK_HIP(hipEventRecord(kdone_[w].get(wk), wk.main_stream()));
+    CEK_HIP(hipEventRecord(kdone_[w].get(wk.dev()), wk.main_stream()));
   }
   ComputeCall c;
   c.arrays = {a};
@@ -268,8 +268,8 @@ uint64_t PeerTraffic::stage_reads(const ComputeCall& c, const std::vector<long l
   for (int w : part) {
     const Worker& wk = *workers_[w];
     wk.set_device();
-    peer_ev_[w].up.get(wk);
-    peer_ev_[w].pulled.get(wk);
+    peer_ev_[w].up.get(wk.dev());
+    peer_ev_[w].pulled.get(wk.dev());
     staged_dev_[w] = 1;
   }
   auto up = [&](int k) { return peer_ev_[part[k]].up.peek(); };
@@ -326,7 +326,7 @@ uint64_t PeerTraffic::stage_reads(const ComputeCall& c, const std::vector<long l
     hipStream_t m = wk.main_stream();
     for (int j = 0; j < P; ++j)
       if (j != k) CEK_HIP(hipStreamWaitEvent(m, pulled(j), 0));
-    CEK_HIP(hipEventRecord(peer_ready_[part[k]].get(wk), m));
+    CEK_HIP(hipEventRecord(peer_ready_[part[k]].get(wk.dev()), m));
   }
   return p2p;
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include "balancer.h"
 #include "events.h"
+#include "worker.h"
 #include "sched_log.h"
 
 namespace cek {
@@ -64,7 +65,7 @@ class PeerTraffic {
   bool call_gathers = false;  // the running call gathers in-process
   // wk's kernels of a gathering call are enqueued on s
   void kernels_done(Worker& wk, hipStream_t s) {
-    if (call_gathers && wk.gpu()) CEK_HIP(hipEventRecord(kdone_[wk.index()].get(wk), s));
+    if (call_gathers && wk.gpu()) CEK_HIP(hipEventRecord(kdone_[wk.index()].get(wk.dev()), s));
   }
   // Work about to run on stream s of wk must see the last gather's copies,
   // and must not overwrite a slice the copies are still reading.

@@ -2,7 +2,7 @@
 // transfer / kernel / event edge the pipelines issue, and every peer copy, is
 // appended as (device, op, logical stream, first work item, work items,
 // event) by the call that issues it.  The logical stream is the id of the
-// Lane it ran on (worker.h: main_lane_id, compute_lane_id, pipe_lane_id).
+// Lane it ran on (lanes.h: main_lane_id, compute_lane_id, pipe_lane_id).
 #pragma once
 #include <mutex>
 #include <string>

@@ -38,8 +38,8 @@ bool Spans::one_per_batch(const SpanModes& m) const {
 static void grow(std::vector<std::pair<Event, Event>>& pool, size_t n, const Worker& wk) {
   while (pool.size() < n) {
     pool.emplace_back();
-    pool.back().first.get(wk, kTimingEventFlags);
-    pool.back().second.get(wk, kTimingEventFlags);
+    pool.back().first.get(wk.dev(), kTimingEventFlags);
+    pool.back().second.get(wk.dev(), kTimingEventFlags);
   }
 }
 
@@ -78,8 +78,8 @@ void Spans::end(Worker& wk, hipStream_t s, const SpanModes& m) {
 void Spans::gap_begin(Worker& wk, hipStream_t s) {
   if (!wk.gpu()) return;
   Dev& d = dev_[wk.index()];
-  const hipEvent_t a = d.gap_a.get(wk, kTimingEventFlags);
-  d.gap_b.get(wk, kTimingEventFlags);
+  const hipEvent_t a = d.gap_a.get(wk.dev(), kTimingEventFlags);
+  d.gap_b.get(wk.dev(), kTimingEventFlags);
   CEK_HIP(hipEventRecord(a, s));
 }
 
@@ -160,8 +160,8 @@ void Spans::record_deferred_ends(int w) {
 Spans::Pending Spans::timeline_begin(Worker& wk, int compute_id, hipStream_t s) {
   Pending sp{wk.index(), compute_id, {}, {}};
   if (wk.gpu()) {
-    sp.begin.get(wk, kTimingEventFlags);
-    sp.end.get(wk, kTimingEventFlags);
+    sp.begin.get(wk.dev(), kTimingEventFlags);
+    sp.end.get(wk.dev(), kTimingEventFlags);
     CEK_HIP(hipEventRecord(sp.begin.peek(), s));
   } else {
     sp.host_begin = now_ms();

@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "events.h"
+#include "worker.h"
 
 namespace cek {
 

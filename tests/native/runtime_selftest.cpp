@@ -2,18 +2,26 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer (sanitizers on
 // the host runtime).  Exercises the balancer law, the JIT front end, and
 // Cores::compute on logical CPU devices: plain, event/driver pipelines,
-// repeats + sync kernel, phase separation, failover.  Exit code 0 = pass.
+// repeats + sync kernel, phase separation, failover; and the worker's parts
+// that need no GPU: lane ids, the job thread, markers and replicas of a CPU
+// worker.  Exit code 0 = pass.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <chrono>
 #include <numeric>
+#include <set>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "balancer.h"
 #include "cores.h"
 #include "device.h"
 #include "jit.h"
+#include "job_thread.h"
+#include "lanes.h"
+#include "worker.h"
 
 using namespace cek;
 
@@ -103,6 +111,120 @@ static void test_byte_chunk() {
           const auto got = byte_chunk(bytes, P, align, k);
           CHECK(got.first == off && got.second == len);
         }
+}
+
+// The 23 lane ids are distinct and below kNoLane; a CPU device has no stream
+// behind any of them, and a stream of nobody's is kNoLane.
+static void test_lane_ids() {
+  std::set<int> ids = {main_lane_id()};
+  for (int q = 0; q < 16; ++q) ids.insert(compute_lane_id(q));
+  for (int h = 0; h < 2; ++h)
+    for (int r = 0; r < 3; ++r) ids.insert(pipe_lane_id(h, r));
+  CHECK(ids.size() == 23);
+  const DeviceInfo cpu = cpu_info(2);
+  for (int qconc : {1, 3}) {
+    LaneTable lanes(cpu, qconc);
+    for (int id : ids) {
+      CHECK(id >= 0 && id < kNoLane);
+      CHECK(lanes.open(id) == nullptr);
+      CHECK(lanes.stream(id) == nullptr);
+    }
+    int created = 0;
+    lanes.for_each_created([&](hipStream_t, int) { ++created; });
+    CHECK(created == 0);
+    int not_a_stream = 0;
+    CHECK(lanes.id_of(reinterpret_cast<hipStream_t>(&not_a_stream)) == kNoLane);
+  }
+}
+
+static void test_job_thread() {
+  const double saved = JobThread::spin_us;
+  for (double us : {0.0, 50.0}) {
+    JobThread::spin_us = us;
+    for (bool spin : {false, true}) {
+      std::atomic<int> ran{0}, first_calls{0};
+      {
+        JobThread jt(spin, [&] { ++first_calls; });
+        for (int round = 0; round < 3; ++round) {
+          for (int i = 0; i < 100; ++i) jt.post([&] { ++ran; });
+          jt.wait();
+          CHECK(ran == 100 * (round + 1));
+        }
+        CHECK(first_calls == 1);
+        // the first of two exceptions comes out of wait() once
+        jt.post([] { throw Error("first"); });
+        jt.post([] { throw Error("second"); });
+        jt.post([&] { ++ran; });
+        std::string what;
+        try {
+          jt.wait();
+        } catch (const Error& e) {
+          what = e.what();
+        }
+        CHECK(what == "first");
+        CHECK(ran == 301);
+        bool clean = true;
+        try {
+          jt.wait();
+        } catch (...) {
+          clean = false;
+        }
+        CHECK(clean);
+        // destruction runs what is still queued: the thread is held in its
+        // current job until the destructor has asked it to stop
+        std::atomic<bool> go{false};
+        jt.post([&] {
+          while (!go) std::this_thread::yield();
+        });
+        for (int i = 0; i < 50; ++i) jt.post([&] { ++ran; });
+        std::thread releaser([&] {
+          std::this_thread::sleep_for(std::chrono::milliseconds(20));
+          go = true;
+        });
+        jt.stop();
+        releaser.join();
+        CHECK(ran == 351);
+      }
+    }
+  }
+  JobThread::spin_us = saved;
+}
+
+// A CPU worker's markers are reached when issued, and its replicas are the
+// host arrays themselves.
+static void test_cpu_worker_parts() {
+  Worker w(cpu_info(2), nullptr, 0, 3, false);
+  CHECK(!w.gpu() && w.main_stream() == nullptr && w.compute_lane(2).id == 3 && w.pipe_lane(1, 2).id == 22);
+  for (int i = 0; i < 3; ++i) {
+    if (i == 0) w.add_marker(nullptr, true);
+    if (i == 1) w.defer_marker(nullptr);
+    if (i == 2) w.flush_markers();
+    CHECK(w.markers_issued() == (i < 2 ? i + 1 : 2));
+    CHECK(w.last_marker() == std::make_pair(-1, static_cast<uint64_t>(w.markers_issued())));
+    CHECK(w.markers_reached() == w.markers_issued());
+    CHECK(!w.has_deferred_markers());
+    CHECK(w.marker_word(-1) == static_cast<uint64_t>(w.markers_issued()));
+  }
+
+  std::vector<float> x(16), y(16);
+  const ArraySpec sx = spec(41, x.data(), 64, 4), sy = spec(42, y.data(), 64, 4);
+  CHECK(w.buffer(sx) == x.data());
+  std::vector<std::pair<uint64_t, void*>> log;
+  w.set_capture_log(&log);
+  CHECK(w.buffer(sx) == x.data() && w.buffer(sy) == y.data() && w.buffer(sx) == x.data());
+  w.set_capture_log(nullptr);
+  CHECK(w.buffer(sy) == y.data());
+  const std::vector<std::pair<uint64_t, void*>> want = {{41, x.data()}, {42, y.data()}, {41, x.data()}};
+  CHECK(log == want);
+  CHECK(!w.buffer_is(41, x.data()));  // a CPU device keeps no replica to compare with
+  CHECK(w.bytes_allocated() == 0);
+  w.release(41);
+  w.release_all();
+  CHECK(w.bytes_allocated() == 0);
+  std::atomic<int> ran{0};
+  w.post([&] { ++ran; });
+  w.wait();
+  CHECK(ran == 1);
 }
 
 static void test_cores() {
@@ -224,6 +346,9 @@ int main() {
   test_balancer();
   test_jit();
   test_byte_chunk();
+  test_lane_ids();
+  test_job_thread();
+  test_cpu_worker_parts();
   test_cores();
   if (failures) {
     std::fprintf(stderr, "%d check(s) failed\n", failures);

@@ -9,7 +9,7 @@ rules in prose.
 ``ClPipeline``.  Per stage the model holds the current and spare input and
 output buffers and the hidden buffers, and per (device, buffer) one replica: a
 GPU-kind device has a replica of its own, a CPU-kind device uses the stage's
-host array (Worker::buffer_impl).  One push runs every stage's kernels in
+host array (Replicas::buffer).  One push runs every stage's kernels in
 order on its current buffers, each device over its range; after every kernel
 of a multi-device stage each device's slice of every output and of every
 hidden buffer that is not read_only goes into every other replica (the

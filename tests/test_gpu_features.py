@@ -148,6 +148,20 @@ def test_enqueue_mode_markers(cr, async_enqueue):
     assert cr.count_markers_reached() >= 20
 
 
+def test_sleeping_stream_waits(gpu):
+    """cores.sleep_waits: a compute's closing wait sleeps on a blocking-sync
+    event recorded on the stream (Worker::wait_stream) instead of
+    hipStreamSynchronize; the results are there when compute() returns."""
+    c = ck.ClNumberCruncher(gpu[0], SRC)
+    assert c.error_code() == 0, c.error_message()
+    c.cores.sleep_waits = True
+    x = ck.ClArray(np.zeros(4096, np.float32))
+    for k in range(3):
+        x.compute(c, 15, "inc", 4096, 256)
+        np.testing.assert_array_equal(x.array, k + 1.0)
+    c.dispose()
+
+
 def test_repeat_with_sync_kernel(cr):
     x = ck.ClArray(np.zeros(4096, np.float32))
     c = ck.ClArray(np.zeros(1, np.int32))

@@ -7,7 +7,7 @@ in prose.
 The model is a numpy emulator of one cruncher: the host arrays and, per
 (device, array), one replica.  A GPU-kind device has a buffer of its own; a
 CPU-kind device, and a zero-copy array on any device, uses the host array
-itself (Worker::buffer_impl).  One call applies, in order: the uploads (from
+itself (Replicas::buffer).  One call applies, in order: the uploads (from
 the host as it was before the call), the kernel on every device's work items,
 the downloads, the keep-resident gather; and it counts the bytes the runtime
 reports as h2d_bytes / d2h_bytes.  The ranges and references are the ones the
