@@ -1,6 +1,7 @@
 // The tile function of the GEMMs whose operands are staged as bytes:
 // sgemm_fp8.hip (plain e4m3fn), sgemm_mxfp8.hip (e4m3fn with E8M0 block
-// scales, MX = true) and sgemm_mxfp4.hip (e2m1, two per byte, F4 = true).
+// scales, MX = true), sgemm_mxfp4.hip (e2m1, two per byte, F4 = true) and
+// sgemm_mxf8f4.hip (e4m3fn A against e2m1 Bt, F4 and A8 = true).
 // Byte geometry, staging and the ping-pong structure are written once here;
 // the two fp8 files differ in the scale operands of the 16x16x128 instruction
 // (and the loads that feed them) and in nothing else, and the 4-bit one in
@@ -18,9 +19,10 @@ typedef long i64x2 __attribute__((ext_vector_type(2)));
 namespace {
 
 // LDS bytes of a tile.  MODE 0: two whole stages (A rows, then Bt rows).
-// MODE 4: two A buffers and three Bt buffers.
-constexpr int gemm8_lds_bytes(int WM, int WN, int FM, int FN, int MODE) {
-  const int a = WM * 16 * FM * 128, b = WN * 16 * FN * 128;
+// MODE 4: two A buffers and three Bt buffers.  A8: A's K-tile is two 128-B
+// sub-tiles.
+constexpr int gemm8_lds_bytes(int WM, int WN, int FM, int FN, int MODE, bool A8 = false) {
+  const int a = WM * 16 * FM * 128 * (A8 ? 2 : 1), b = WN * 16 * FN * 128;
   return MODE == 4 ? 2 * a + 3 * b : 2 * (a + b);
 }
 
@@ -49,6 +51,11 @@ __device__ __forceinline__ void cek_static_for(F&& f) {
 // bytes and a K-tile of 128 B holds 256 k: two scaled instructions per
 // fragment pair, step s on the 16 B of read s with the scales of 128-k step
 // 2·kt + s.  Everything written in bytes stays as it is.
+// A8 (with F4): A alone is e4m3fn, one element per byte (sgemm_mxf8f4.hip).
+// Bt, its staging and both scale arrays are F4's.  A's row pitch is K bytes
+// and its K-tile of 256 k two 128-B sub-tiles [2][BM][128], sub-tile h staged
+// as byte K-tile 2·kt + h; step s multiplies the two 16-B reads of sub-tile s
+// (the MXFP8 operand of that 128-k step) by the 16 B of Bt's read s.
 // OUT: what is stored.  GEMM8_OUT_F32 (the default): C as fp32, tile-major in
 // fragment order.  Otherwise (gemm8_out.h) `C` points to the row-major [M][N]
 // output in that mode's format, `SY` to its row-major scale bytes (MX modes)
@@ -56,7 +63,7 @@ __device__ __forceinline__ void cek_static_for(F&& f) {
 // kernels do not read.  Nothing above the store depends on OUT, so the
 // accumulators are those of the plain kernel with the same tile.
 template <int WM, int WN, int FM, int FN, int MODE, bool X128, bool MX = false, bool F4 = false,
-          int OUT = GEMM8_OUT_F32>
+          int OUT = GEMM8_OUT_F32, bool A8 = false>
 __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const uint8_t* __restrict__ A,
                                            const uint8_t* __restrict__ Bt, float* __restrict__ C, char* smem,
                                            long long off, const int* __restrict__ SAp = nullptr,
@@ -65,11 +72,13 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
   static_assert(MODE == 0 || MODE == 4, "MODE is 0 or 4");
   static_assert(!MX || (X128 && FM % 4 == 0 && FN % 4 == 0), "MX: scaled instruction, 64-row scale groups");
   static_assert(!F4 || MX, "F4: block-scaled only");
+  static_assert(!A8 || F4, "A8: e4m3 A against e2m1 Bt");
   constexpr int BM = WM * 16 * FM, BN = WN * 16 * FN, BK = 128;
   constexpr int NWAVES = WM * WN, NT = 64 * NWAVES;
-  constexpr int A_BYTES = BM * BK, B_BYTES = BN * BK, STAGE = A_BYTES + B_BYTES;
+  constexpr int A_SUB = BM * BK;  // one 128-B sub-tile of A (A8: two per K-tile)
+  constexpr int A_BYTES = A_SUB * (A8 ? 2 : 1), B_BYTES = BN * BK, STAGE = A_BYTES + B_BYTES;
   constexpr int STAGERS = MODE == 4 ? NWAVES / 2 : NWAVES;
-  constexpr int A_INSTR = A_BYTES / 1024 / STAGERS;
+  constexpr int A_INSTR = A_SUB / 1024 / STAGERS;  // per sub-tile
   constexpr int B_INSTR = B_BYTES / 1024 / STAGERS;
 
   const int M = dims[0], N = dims[1], K = dims[2], GM = dims[3] > 0 ? dims[3] : 1;
@@ -82,24 +91,36 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
   if (!cek_tile_lookup(dims, GM, t, ntm, ntn, tm, tn)) return;
   const int m0 = tm * BM, n0 = tn * BN;
   const int KB = F4 ? K / 2 : K;  // row pitch in bytes
+  const int KA = A8 ? K : KB;     // A's, where it differs
   const int nk = KB / BK, ks = 0;
 
   // ---- staging (geometry: gemm_parts.h) ----
   const unsigned lane_off = cek_stage_lane_off<1>(lane, KB);
+  const unsigned lane_off_a = A8 ? cek_stage_lane_off<1>(lane, KA) : lane_off;
   const int sw = MODE == 4 ? wave % (NWAVES / 2) : wave;  // staging wave index
-  const char* a_wave = (const char*)(A + (size_t)(m0 + sw * A_INSTR * 8) * KB);
+  const char* a_wave = (const char*)(A + (size_t)(m0 + sw * A_INSTR * 8) * KA);
   const char* b_wave = (const char*)(Bt + (size_t)(n0 + sw * B_INSTR * 8) * KB);
+  // A's K-tile kt to `dst` (A8: its two sub-tiles, byte K-tiles 2·kt and 2·kt + 1)
+  auto stage_a = [&](int kt, char* dst) {
+    if constexpr (A8) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int kb = 2 * kt + h;
+        cek_stage_rows<A_INSTR, 1>(a_wave, lane_off_a, KA, ks, kb, dst + h * A_SUB, sw);
+      }
+    } else {
+      cek_stage_rows<A_INSTR, 1>(a_wave, lane_off, KB, ks, kt, dst, sw);
+    }
+  };
   // MODE 0: K-tile kt into whole stage `buf` (A rows, then Bt rows)
   auto stage = [&](int buf, int kt) {
-    cek_stage_rows<A_INSTR, 1>(a_wave, lane_off, KB, ks, kt, smem + buf * STAGE, sw);
+    stage_a(kt, smem + buf * STAGE);
     cek_stage_rows<B_INSTR, 1>(b_wave, lane_off, KB, ks, kt, smem + buf * STAGE + A_BYTES, sw);
   };
   // MODE 4: two A buffers followed by three Bt buffers
   char* const a_base = smem;
   char* const b_base = smem + 2 * A_BYTES;
-  auto stage_a4 = [&](int kt) {
-    cek_stage_rows<A_INSTR, 1>(a_wave, lane_off, KB, ks, kt, a_base + (kt & 1) * A_BYTES, sw);
-  };
+  auto stage_a4 = [&](int kt) { stage_a(kt, a_base + (kt & 1) * A_BYTES); };
   auto stage_b4 = [&](int kt) {
     cek_stage_rows<B_INSTR, 1>(b_wave, lane_off, KB, ks, kt, b_base + (kt % 3) * B_BYTES, sw);
   };
@@ -179,12 +200,22 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
   };
 
   i32x4 fa[2][FM], fb[2][FN];
+  i32x4 fah[2][FM];  // A8: the high 16 B of step s's A operand (fa[s]: the low)
   // k block s of a K-tile: A rows from ab, Bt rows from bb (b_off includes A_BYTES)
+  // A8: step s, A's two reads inside sub-tile s
   auto ld = [&](int s, const char* ab, const char* bb) {
 #pragma unroll
     for (int j = 0; j < FN; ++j) fb[s][j] = *(const i32x4*)(bb + b_off[s] + j * 2048);
+    if constexpr (A8) {
 #pragma unroll
-    for (int i = 0; i < FM; ++i) fa[s][i] = *(const i32x4*)(ab + a_off[s] + i * 2048);
+      for (int i = 0; i < FM; ++i) {
+        fa[s][i] = *(const i32x4*)(ab + s * A_SUB + a_off[0] + i * 2048);
+        fah[s][i] = *(const i32x4*)(ab + s * A_SUB + a_off[1] + i * 2048);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < FM; ++i) fa[s][i] = *(const i32x4*)(ab + a_off[s] + i * 2048);
+    }
   };
   // the two 16x16x32 steps of k block s: the low, then the high 8 B of the read
   auto mma = [&](int s) {
@@ -240,9 +271,26 @@ __device__ __forceinline__ void gemm8_tile(const int* __restrict__ dims, const u
       });
     });
   };
+  // A8: the same two steps with A's 32-B e4m3 operand (format 0) against
+  // Bt's 16 B of e2m1 (format 4), in mma128f4's issue order
+  auto mma128f8f4 = [&] {
+    cek_static_for<0, 2>([&](auto sc) {
+      cek_static_for<0, FM>([&](auto ic) {
+        cek_static_for<0, FN>([&](auto jc) {
+          constexpr int s = decltype(sc)::value, i = decltype(ic)::value, j = decltype(jc)::value;
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+              __builtin_shufflevector(fa[s][i], fah[s][i], 0, 1, 2, 3, 4, 5, 6, 7),
+              __builtin_shufflevector(fb[s][j], fb[s][j], 0, 1, 2, 3, -1, -1, -1, -1), acc[i][j], 0, 4, i & 3,
+              sa[s * SA_G + i / 4], j & 3, sb[s * SB_G + j / 4]);
+        });
+      });
+    });
+  };
   auto mmaall = [&] {
     __builtin_amdgcn_s_setprio(1);
-    if constexpr (F4) {
+    if constexpr (A8) {
+      mma128f8f4();
+    } else if constexpr (F4) {
       mma128f4();
     } else if constexpr (MX) {
       mma128mx();

@@ -1,7 +1,7 @@
 """Range-partitioned GEMMs: bf16 (the "SGEMM 8192² bf16" config of
 BASELINE.json), fp32 on the fp32 matrix cores, fp8 (OCP e4m3fn), MXFP8
-(e4m3fn with one E8M0 scale per block of 32) and MXFP4 (e2m1, two per byte,
-with the same scales).
+(e4m3fn with one E8M0 scale per block of 32), MXFP4 (e2m1, two per byte,
+with the same scales) and the mixed MXFP8 × MXFP4 form (8-bit A, 4-bit B).
 
 ``C = A · Bᵀ`` with A ``[M][K]`` and Bt ``[N][K]`` bf16 row-major, C fp32 in
 tile-major layout (see ``kernels/sgemm_bf16.hip``).  The global range is one
@@ -184,6 +184,22 @@ MX_OUT_LIB = "sgemm_mx_out"
 MX_OUT_PACK_ID = 0x4D70
 MX_ACTIVATIONS = {None: 0, "relu": 1}  # dims[5]
 
+# Mixed MXFP8 × MXFP4 tiles (kernels/sgemm_mxf8f4.hip): A e4m3fn, Bt e2m1, a
+# K-tile of 256 k as two scaled instructions with one format per operand.
+# Throughput beside the MXFP8 256x256pbx of the same run: profiles/gemm_mxf8f4.md.
+MXF8F4_TILES = {
+    # balanced-DMA ping-pong, byte for byte the MXFP8 256x256pbx loop (A's
+    # K-tile is 256 B per row, so the tile has half the rows): the GemmMxFp8Fp4 default
+    "128x256pbx": (128, 256, 512, "cek_sgemm_mxf8f4_128x256pbx"),
+    # one LDS stage in flight, 4 waves: the simple kernel the other is judged against
+    "128x128": (128, 128, 256, "cek_sgemm_mxf8f4_128x128"),
+}
+MXF8F4_TILE_WAVES = {"128x256pbx": (2, 4, 4, 4), "128x128": (2, 2, 4, 4)}
+# their output modes (kernels/sgemm_mxf8f4_out.hip), keyed like MX_OUT_KERNELS
+MXF8F4_OUT_KERNELS = {("mxf8f4", tile, out): f"cek_sgemm_mxf8f4_{tile}_{'bf16' if out == 'bfloat16' else out}"
+                      for tile in MXF8F4_TILES for out in MX_OUTPUTS}
+MXF8F4_OUT_LIB = "sgemm_mxf8f4_out"
+
 # tiles whose kernel stores C row-major ([M][N]) instead of tile-major
 ROW_MAJOR_TILES = {"256x256pbr"}
 # tiles with a split-K kernel variant ("<kernel>_sk", arrays + W + counters)
@@ -261,8 +277,8 @@ class GemmBf16:
         # the helper claims the hand-back at once — forced fall-backs)
         self.dims = ClArray(np.array([M, N, K, group_m, self.split_k, shift, 0, int(handover_spin_limit)], np.int32))
         self.dims.write = False
-        self.A = ClArray(M * K // self.PER_ITEM, self.OPERAND_DTYPE)
-        self.B = ClArray(N * K // self.PER_ITEM, self.OPERAND_DTYPE)
+        self.A = ClArray(M * K // self._per_item("A"), self._operand_dtype("A"))
+        self.B = ClArray(N * K // self._per_item("B"), self._operand_dtype("B"))
         scales = self._alloc_scales()
         for a in (self.A, self.B, *scales):
             a.write = False
@@ -285,6 +301,15 @@ class GemmBf16:
         self._uploaded = False
         self.wave_granularity = wave_granularity
         self._orders = {}  # compute id -> shell panels of its tile order (0: grouped)
+
+    def _operand_dtype(self, name: str):
+        """Storage dtype of operand ``name`` (``"A"`` / ``"B"``): one for both
+        but in the mixed-format class."""
+        return self.OPERAND_DTYPE
+
+    def _per_item(self, name: str) -> int:
+        """Elements per storage item of operand ``name``."""
+        return self.PER_ITEM
 
     def _alloc_scales(self) -> tuple:
         """Allocate what a format keeps beside ``A`` and ``B`` (the MX formats:
@@ -341,7 +366,7 @@ class GemmBf16:
     def _row_items(self) -> int:
         """Storage items of one operand row in ``A`` / ``B``: K, one per
         element (GemmMxFp4: K/2 bytes of two elements each)."""
-        return self.K // self.PER_ITEM
+        return self.K // self._per_item("A")
 
     def _group_work_items(self) -> int:
         """Work items of one tile group (``group_m`` tile rows × every tile
@@ -822,6 +847,16 @@ class GemmMxFp8(GemmBf16):
     _to_mx = staticmethod(to_mxfp8)  # [rows][K] fp32 values -> (what A / B store, scale bytes)
 
     FORMAT = "mxfp8"  # the output mode of a producer whose Y this class reads as an operand
+    OUT_KERNELS = MX_OUT_KERNELS  # (FORMAT, tile, out) -> output-mode kernel, in library OUT_LIB
+    OUT_LIB = MX_OUT_LIB
+
+    def _format_of(self, name: str) -> str:
+        """The MX format of operand ``name``: what :meth:`take_operand` asks of a producer."""
+        return self.FORMAT
+
+    def _to_mx_of(self, name: str):
+        """``[rows][K]`` fp32 values -> (what operand ``name`` stores, scale bytes)."""
+        return self._to_mx
 
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
@@ -839,11 +874,11 @@ class GemmMxFp8(GemmBf16):
             raise ValueError("act needs an output mode (out=...): the plain kernels store the accumulator as it is")
         self.out, self.act = out, act
         if out is not None:
-            self.LIBS = type(self).LIBS + (MX_OUT_LIB,)
+            self.LIBS = type(self).LIBS + (self.OUT_LIB,)
         super().__init__(M, N, K, devices, tile, cruncher, fill, seed, group_m, wave_granularity=wave_granularity)
         if out is None:
             return
-        self.kernel = MX_OUT_KERNELS[self.FORMAT, tile, out]
+        self.kernel = self.OUT_KERNELS[self.FORMAT, tile, out]
         self.dims.array[5] = MX_ACTIVATIONS[act]
         if self.cr.number_of_devices > 1 and (M // self.BM) % max(1, group_m):
             raise ValueError(f"an output mode on several devices needs whole tile groups: (M / {self.BM}) = "
@@ -926,10 +961,10 @@ class GemmMxFp8(GemmBf16):
         """Per operand, A then B: uniform [−1, 1) values times ``2^u`` per
         block, u an integer uniform in [−12, 12], quantised by the format."""
         K = self.K
-        for arr, sc, rows in ((self.A, self.SA, self.M), (self.B, self.SB, self.N)):
+        for name, arr, sc, rows in (("A", self.A, self.SA, self.M), ("B", self.B, self.SB, self.N)):
             x = rng.uniform(-1, 1, (rows, K // MX_BLOCK, MX_BLOCK))
             x = np.ldexp(x, rng.integers(-12, 13, (rows, K // MX_BLOCK, 1)))
-            codes, scales = self._to_mx(x.astype(np.float32).reshape(rows, K))
+            codes, scales = self._to_mx_of(name)(x.astype(np.float32).reshape(rows, K))
             arr.array[:] = codes.ravel()
             sc.array[:] = scales.ravel()
 
@@ -967,7 +1002,7 @@ class GemmMxFp8(GemmBf16):
             for k in (self.kernel, PACK_KERNEL):
                 if k not in have:
                     raise ClComputeError(f"the cruncher has no kernel {k!r}: it was built without "
-                                         f"library({MX_OUT_LIB!r}) or library('mx_quantize')")
+                                         f"library({self.OUT_LIB!r}) or library('mx_quantize')")
         for name in self._taken:  # shared with their producer, which sets its own flags for its calls
             for a in ((self.A, self._SAp) if name == "A" else (self.B, self._SBp)):
                 a.write = a.gather_resident = a.partial_read = False
@@ -987,9 +1022,9 @@ class GemmMxFp8(GemmBf16):
         they are."""
         if name not in ("A", "B"):
             raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
-        out = getattr(producer, "out", None)
-        if out != self.FORMAT:
-            raise ValueError(f"format mismatch: {type(self).__name__} takes a producer with out={self.FORMAT!r} "
+        out, fmt = getattr(producer, "out", None), self._format_of(name)
+        if out != fmt:
+            raise ValueError(f"format mismatch: {type(self).__name__} takes a producer with out={fmt!r} "
                              f"(got out={out!r})")
         rows = self.M if name == "A" else self.N
         if producer.M != rows:
@@ -1201,3 +1236,72 @@ class GemmMxFp4(GemmMxFp8):
         scales stay resident for the next resident :meth:`run`; the host
         arrays are stale until :meth:`sync_operands` unless ``download``."""
         self._quantize_with(MxFp4Quantizer, 0x4D60, name, x, src, download)
+
+
+class GemmMxFp8Fp4(GemmMxFp8):
+    """``C = (A∘SA) · (B∘SB)ᵀ`` with MXFP8 activations against MXFP4 weights
+    ("W4A8"): ``A`` ``[M][K]`` e4m3fn bytes (``ClArray(…, "float8_e4m3fn")``,
+    as in :class:`GemmMxFp8`), ``B`` ``[N][K/2]`` packed e2m1
+    (``ClArray(…, "float4_e2m1fn_x2")``, the low nibble the even k, as in
+    :class:`GemmMxFp4`), ``SA`` (``M·K/32``) and ``SB`` (``N·K/32``) E8M0 scale
+    bytes, one per 32 consecutive k; fp32 accumulation and output, C
+    tile-major in fragment order like :class:`GemmBf16`.  B's device and
+    upload bytes are half of :class:`GemmMxFp8`'s, and A keeps its 8 bits.
+
+    Only this orientation exists (A 8-bit, B 4-bit): 4-bit A against 8-bit B is
+    the same product transposed, ``(B∘SB) · (A∘SA)ᵀ = Cᵀ`` with the operands'
+    roles exchanged.
+
+    ``fill="random"`` is :class:`GemmMxFp8`'s draw through :func:`to_mxfp8`
+    for A and :func:`to_mxfp4` for B.  K must be a multiple of 256 (one K-tile
+    of 128 bytes of B).  Every host reference decodes each operand by its own
+    format.  The shell paths are not available.
+
+    ``quantize("A", x)`` runs :class:`~cekirdekler_amd.ops.quantize.MxFp8Quantizer`
+    and ``quantize("B", x)`` :class:`~cekirdekler_amd.ops.quantize.MxFp4Quantizer`,
+    with :meth:`GemmMxFp8.quantize`'s residency rules; ``take_operand("A", p)``
+    needs ``p.out == "mxfp8"`` and ``take_operand("B", p)`` ``p.out ==
+    "mxfp4"``.  ``out=`` and ``act=`` are :class:`GemmMxFp8`'s, through
+    ``kernels/sgemm_mxf8f4_out.hip``.
+
+    Numerics: profiles/gemm_mxf8f4.md has what the single-instruction probe of
+    the mixed form measured; A's NaN codes and a scale byte ``0xFF`` poison
+    their row or column of C as in the pure formats."""
+
+    TILE_TABLE = MXF8F4_TILES
+    TILE_GEOM = MXF8F4_TILE_WAVES
+    FORMAT = "mxf8f4"  # the key of OUT_KERNELS; the operands' formats are _format_of's
+    OUT_KERNELS = MXF8F4_OUT_KERNELS
+    OUT_LIB = MXF8F4_OUT_LIB
+    K_MULTIPLE = 256
+    LIBS = ("sgemm_mxf8f4", "mx_quantize", "mx4_quantize")
+    # per operand: (storage dtype, elements per item, MX format, host codec, quantizer, its base compute id)
+    OPERANDS = {"A": ("float8_e4m3fn", 1, "mxfp8", to_mxfp8, MxFp8Quantizer, 0x4D58),
+                "B": ("float4_e2m1fn_x2", 2, "mxfp4", to_mxfp4, MxFp4Quantizer, 0x4D60)}
+
+    def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "128x256pbx",
+                 cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
+                 group_m: int = 4, wave_granularity: bool | None = None, out: str | None = None,
+                 act: str | None = None):
+        super().__init__(M, N, K, devices, tile, cruncher, fill, seed, group_m, wave_granularity, out, act)
+
+    def _operand_dtype(self, name: str):
+        return self.OPERANDS[name][0]
+
+    def _per_item(self, name: str) -> int:
+        return self.OPERANDS[name][1]
+
+    def _format_of(self, name: str) -> str:
+        return self.OPERANDS[name][2]
+
+    def _to_mx_of(self, name: str):
+        return self.OPERANDS[name][3]
+
+    def quantize(self, name: str, x, src: str | None = None, download: bool = False) -> None:
+        """:meth:`GemmMxFp8.quantize` by the operand's own format: ``"A"`` to
+        MXFP8 (bit for bit :func:`to_mxfp8`), ``"B"`` to MXFP4 (bit for bit
+        :func:`to_mxfp4`), on the devices of this GEMM's cruncher."""
+        if name not in ("A", "B"):
+            raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
+        quantizer, base_id = self.OPERANDS[name][4:]
+        self._quantize_with(quantizer, base_id, name, x, src, download)

@@ -34,6 +34,10 @@ LIBRARY = {
     # bf16, or MXFP8 / MXFP4 codes with row-major scales, blocks of 32 along N
     "sgemm_mx_out": [f"cek_sgemm_{fmt}_{tile}_{out}" for fmt in ("mxfp8", "mxfp4")
                      for tile in ("128x128", "256x256pbx") for out in ("bf16", "mxfp8", "mxfp4")],
+    # MXFP8 A against MXFP4 Bt (GemmMxFp8Fp4), and the same tiles with the next layer's operand as output
+    "sgemm_mxf8f4": ["cek_sgemm_mxf8f4_128x128", "cek_sgemm_mxf8f4_128x256pbx"],
+    "sgemm_mxf8f4_out": [f"cek_sgemm_mxf8f4_{tile}_{out}" for tile in ("128x128", "128x256pbx")
+                         for out in ("bf16", "mxfp8", "mxfp4")],
     # device-side MXFP8 quantisation (ops/quantize.py): fp32 / bf16 → codes + scales, scale repack
     "mx_quantize": ["cek_mx_quantize_f32", "cek_mx_quantize_bf16", "cek_mx_pack_scales"],
     # device-side MXFP4 quantisation: fp32 / bf16 → packed e2m1 codes + scales (the repack is mx_quantize's)
@@ -58,6 +62,8 @@ ARITY = {
     **{k: 6 for k in LIBRARY["sgemm_mxfp8"]},  # dims, A, Bt, packed SA, packed SB, C
     **{k: 6 for k in LIBRARY["sgemm_mxfp4"]},  # the same six; A and Bt hold two e2m1 elements per byte
     **{k: (6 if k.endswith("_bf16") else 7) for k in LIBRARY["sgemm_mx_out"]},  # dims, A, Bt, SAp, SBp, Y [, SY]
+    **{k: 6 for k in LIBRARY["sgemm_mxf8f4"]},  # the same six; A one e4m3 element per byte, Bt two e2m1
+    **{k: (6 if k.endswith("_bf16") else 7) for k in LIBRARY["sgemm_mxf8f4_out"]},
     **{k: 3 for k in LIBRARY["mx_quantize"]},  # X, codes, scales / dims, S, P
     **{k: 3 for k in LIBRARY["mx4_quantize"]},  # X, codes (two per byte), scales
     **{k: 3 for k in LIBRARY["mandelbrot"]},
