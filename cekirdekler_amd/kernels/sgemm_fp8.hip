@@ -24,17 +24,10 @@
 // The tile function is gemm8_tile.h, shared with sgemm_mxfp8.hip.
 #include "gemm8_tile.h"
 
-#define CEK_GEMM8_KERNEL(NAME, WM, WN, FM, FN, MODE, X128)                                                  \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(const int* dims, const uint8_t* A,        \
-                                                                    const uint8_t* Bt, float* C, CEK_HIDDEN) { \
-    __shared__ __attribute__((aligned(16))) char smem[gemm8_lds_bytes(WM, WN, FM, FN, MODE)];                \
-    gemm8_tile<WM, WN, FM, FN, MODE, X128>(dims, A, Bt, C, smem, __cek_off);                                 \
-  }
-
 // 128×128 tiles, 4 waves (2×2, 64×64 each), 64 KiB LDS, one stage in flight:
 // the simple kernel the others are judged against.
-CEK_GEMM8_KERNEL(cek_sgemm_fp8_128x128, 2, 2, 4, 4, 0, false)
+CEK_GEMM8_KERNEL(cek_sgemm_fp8_128x128, 2, 2, 4, 4, 0, GEMM8_K32, GEMM8_E4M3, GEMM8_E4M3)
 // 256×256 tiles, 8 waves (2×4, 128×64 each), balanced-DMA ping-pong, 160 KiB LDS.
-CEK_GEMM8_KERNEL(cek_sgemm_fp8_256x256pb, 2, 4, 8, 4, 4, false)
+CEK_GEMM8_KERNEL(cek_sgemm_fp8_256x256pb, 2, 4, 8, 4, 4, GEMM8_K32, GEMM8_E4M3, GEMM8_E4M3)
 // the same with the scaled 16x16x128 instruction (unit scales)
-CEK_GEMM8_KERNEL(cek_sgemm_fp8_256x256pbx, 2, 4, 8, 4, 4, true)
+CEK_GEMM8_KERNEL(cek_sgemm_fp8_256x256pbx, 2, 4, 8, 4, 4, GEMM8_UNIT, GEMM8_E4M3, GEMM8_E4M3)

@@ -19,26 +19,8 @@
 // whole tile groups (ops/gemm.py splits that way on several devices).
 #include "gemm8_tile.h"
 
-#define CEK_SY_PARAMS_0
-#define CEK_SY_PARAMS_1 uint8_t *SY,
-#define CEK_SY_ARG_0 nullptr
-#define CEK_SY_ARG_1 SY
-#define CEK_GEMM_MX_OUT_KERNEL(NAME, F4, WM, WN, FM, FN, MODE, OUT, HAS_SY)                                      \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                               \
-      const int* dims, const uint8_t* A, const uint8_t* Bt, const int* SAp, const int* SBp, uint8_t* Y,          \
-      CEK_SY_PARAMS_##HAS_SY CEK_HIDDEN) {                                                                        \
-    __shared__ __attribute__((aligned(16))) char smem[gemm8_lds_bytes(WM, WN, FM, FN, MODE)];                    \
-    gemm8_tile<WM, WN, FM, FN, MODE, true, true, F4, OUT>(dims, A, Bt, reinterpret_cast<float*>(Y), smem,        \
-                                                          __cek_off, SAp, SBp, CEK_SY_ARG_##HAS_SY);             \
-  }
-// the three outputs of one operand format and tile
-#define CEK_GEMM_MX_OUT_TILE(STEM, F4, WM, WN, FM, FN, MODE)                                  \
-  CEK_GEMM_MX_OUT_KERNEL(STEM##_bf16, F4, WM, WN, FM, FN, MODE, GEMM8_OUT_BF16, 0)            \
-  CEK_GEMM_MX_OUT_KERNEL(STEM##_mxfp8, F4, WM, WN, FM, FN, MODE, GEMM8_OUT_MXFP8, 1)          \
-  CEK_GEMM_MX_OUT_KERNEL(STEM##_mxfp4, F4, WM, WN, FM, FN, MODE, GEMM8_OUT_MXFP4, 1)
-
-// the tiles of sgemm_mxfp8.hip and sgemm_mxfp4.hip
-CEK_GEMM_MX_OUT_TILE(cek_sgemm_mxfp8_128x128, false, 2, 2, 4, 4, 0)
-CEK_GEMM_MX_OUT_TILE(cek_sgemm_mxfp8_256x256pbx, false, 2, 4, 8, 4, 4)
-CEK_GEMM_MX_OUT_TILE(cek_sgemm_mxfp4_128x128, true, 2, 2, 4, 4, 0)
-CEK_GEMM_MX_OUT_TILE(cek_sgemm_mxfp4_256x256pbx, true, 2, 4, 8, 4, 4)
+// the tiles of sgemm_mxfp8.hip and sgemm_mxfp4.hip, the three outputs of each
+CEK_GEMM8_MX_OUT_TILE(cek_sgemm_mxfp8_128x128, 2, 2, 4, 4, 0, GEMM8_E4M3, GEMM8_E4M3)
+CEK_GEMM8_MX_OUT_TILE(cek_sgemm_mxfp8_256x256pbx, 2, 4, 8, 4, 4, GEMM8_E4M3, GEMM8_E4M3)
+CEK_GEMM8_MX_OUT_TILE(cek_sgemm_mxfp4_128x128, 2, 2, 4, 4, 0, GEMM8_E2M1, GEMM8_E2M1)
+CEK_GEMM8_MX_OUT_TILE(cek_sgemm_mxfp4_256x256pbx, 2, 4, 8, 4, 4, GEMM8_E2M1, GEMM8_E2M1)

@@ -16,7 +16,7 @@
 // The instruction is v_mfma_scale_f32_16x16x128_f8f6f4 with one format
 // selector per operand: cbsz = 0 (e4m3, a 32-B operand, 8 VGPRs) for A and
 // blgp = 4 (e2m1, 16 B, 4 VGPRs) for Bt.  The tile function is gemm8_tile.h's
-// with F4 and A8 set.  Bt is sgemm_mxfp4.hip's operand in every respect: LDS
+// with FA = GEMM8_E4M3 and FB = GEMM8_E2M1.  Bt is sgemm_mxfp4.hip's operand in every respect: LDS
 // rows of 128 B = 256 k, row pitch K/2, staging, the ring of three buffers,
 // the read b_off[s] of step s.  A is sgemm_mxfp8.hip's operand twice over:
 // the K-tile of 256 k is two 128-B sub-tiles [2][BM][128], each staged by
@@ -35,7 +35,7 @@
 //   - scales, both operands: the byte of lane l applies to row l % 16 and MX
 //     block q = l / 16 of the step; op_sel = b picks bits 8b .. 8b+7.
 // So both public layouts are the device layouts, and the packed scales are
-// pack_mx_scales's for both operands, addressed by 128-k step as under F4:
+// pack_mx_scales's for both operands, addressed by 128-k step as in sgemm_mxfp4.hip:
 // K-tile kt uses steps 2kt and 2kt + 1, M (N) dwords apart.
 //
 // Tiles.  128×128 (4 waves, 2×2, one stage in flight): 2·(32 + 16) KiB = 96
@@ -85,17 +85,8 @@
 // the 4-bit B buys is half of B's memory and upload.
 #include "gemm8_tile.h"
 
-#define CEK_GEMM84MX_KERNEL(NAME, WM, WN, FM, FN, MODE)                                                          \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(const int* dims, const uint8_t* A,             \
-                                                                    const uint8_t* Bt, const int* SAp,            \
-                                                                    const int* SBp, float* C, CEK_HIDDEN) {       \
-    __shared__ __attribute__((aligned(16))) char smem[gemm8_lds_bytes(WM, WN, FM, FN, MODE, true)];              \
-    gemm8_tile<WM, WN, FM, FN, MODE, true, true, true, GEMM8_OUT_F32, true>(dims, A, Bt, C, smem, __cek_off,     \
-                                                                             SAp, SBp);                           \
-  }
-
 // 128×128 tiles, 4 waves (2×2, 64×64 each), 96 KiB LDS, one stage in flight:
 // the simple kernel the production tile is judged against.
-CEK_GEMM84MX_KERNEL(cek_sgemm_mxf8f4_128x128, 2, 2, 4, 4, 0)
+CEK_GEMM8_MX_KERNEL(cek_sgemm_mxf8f4_128x128, 2, 2, 4, 4, 0, GEMM8_E4M3, GEMM8_E2M1)
 // 128×256 tiles, 8 waves (2×4, 64×64 each), balanced-DMA ping-pong, 160 KiB LDS.
-CEK_GEMM84MX_KERNEL(cek_sgemm_mxf8f4_128x256pbx, 2, 4, 4, 4, 4)
+CEK_GEMM8_MX_KERNEL(cek_sgemm_mxf8f4_128x256pbx, 2, 4, 4, 4, 4, GEMM8_E4M3, GEMM8_E2M1)

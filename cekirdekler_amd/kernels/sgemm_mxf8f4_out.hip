@@ -12,25 +12,6 @@
 // Arrays: dims, A, Bt, SAp, SBp, Y and, for the MX outputs, SY.
 #include "gemm8_tile.h"
 
-#define CEK_SY_PARAMS_0
-#define CEK_SY_PARAMS_1 uint8_t *SY,
-#define CEK_SY_ARG_0 nullptr
-#define CEK_SY_ARG_1 SY
-#define CEK_GEMM84_OUT_KERNEL(NAME, WM, WN, FM, FN, MODE, OUT, HAS_SY)                                           \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(                                               \
-      const int* dims, const uint8_t* A, const uint8_t* Bt, const int* SAp, const int* SBp, uint8_t* Y,          \
-      CEK_SY_PARAMS_##HAS_SY CEK_HIDDEN) {                                                                        \
-    __shared__ __attribute__((aligned(16))) char smem[gemm8_lds_bytes(WM, WN, FM, FN, MODE, true)];              \
-    gemm8_tile<WM, WN, FM, FN, MODE, true, true, true, OUT, true>(dims, A, Bt, reinterpret_cast<float*>(Y),      \
-                                                                  smem, __cek_off, SAp, SBp,                      \
-                                                                  CEK_SY_ARG_##HAS_SY);                           \
-  }
-// the three outputs of one tile
-#define CEK_GEMM84_OUT_TILE(STEM, WM, WN, FM, FN, MODE)                                \
-  CEK_GEMM84_OUT_KERNEL(STEM##_bf16, WM, WN, FM, FN, MODE, GEMM8_OUT_BF16, 0)          \
-  CEK_GEMM84_OUT_KERNEL(STEM##_mxfp8, WM, WN, FM, FN, MODE, GEMM8_OUT_MXFP8, 1)        \
-  CEK_GEMM84_OUT_KERNEL(STEM##_mxfp4, WM, WN, FM, FN, MODE, GEMM8_OUT_MXFP4, 1)
-
-// the tiles of sgemm_mxf8f4.hip
-CEK_GEMM84_OUT_TILE(cek_sgemm_mxf8f4_128x128, 2, 2, 4, 4, 0)
-CEK_GEMM84_OUT_TILE(cek_sgemm_mxf8f4_128x256pbx, 2, 4, 4, 4, 4)
+// the tiles of sgemm_mxf8f4.hip, the three outputs of each
+CEK_GEMM8_MX_OUT_TILE(cek_sgemm_mxf8f4_128x128, 2, 2, 4, 4, 0, GEMM8_E4M3, GEMM8_E2M1)
+CEK_GEMM8_MX_OUT_TILE(cek_sgemm_mxf8f4_128x256pbx, 2, 4, 4, 4, 4, GEMM8_E4M3, GEMM8_E2M1)

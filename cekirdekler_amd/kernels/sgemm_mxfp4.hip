@@ -10,7 +10,7 @@
 //   (dims[2] = K in elements); arrays: dims, A, Bt, SAp, SBp, C.
 //   M % BM = N % BN = K % 256 = 0.
 //
-// The tile function is gemm8_tile.h's with F4 set.  That file is written in
+// The tile function is gemm8_tile.h's with both formats GEMM8_E2M1.  That file is written in
 // bytes, and in bytes nothing changes: LDS rows of 128 B, 16-B chunks
 // XOR-swizzled by row & 7, staging by cek_stage_rows<…, 1> with a row pitch of
 // K/2, the ping-pong loop of MODE 4.  A 128-B row now holds 256 k, which is
@@ -80,16 +80,8 @@
 // has 32, which this loop hardly hides behind anything).
 #include "gemm8_tile.h"
 
-#define CEK_GEMM4MX_KERNEL(NAME, WM, WN, FM, FN, MODE)                                                          \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(const int* dims, const uint8_t* A,            \
-                                                                    const uint8_t* Bt, const int* SAp,            \
-                                                                    const int* SBp, float* C, CEK_HIDDEN) {       \
-    __shared__ __attribute__((aligned(16))) char smem[gemm8_lds_bytes(WM, WN, FM, FN, MODE)];                    \
-    gemm8_tile<WM, WN, FM, FN, MODE, true, true, true>(dims, A, Bt, C, smem, __cek_off, SAp, SBp);               \
-  }
-
 // 128×128 tiles, 4 waves (2×2, 64×64 each), 64 KiB LDS, one stage in flight:
 // the simple kernel the production tile is judged against.
-CEK_GEMM4MX_KERNEL(cek_sgemm_mxfp4_128x128, 2, 2, 4, 4, 0)
+CEK_GEMM8_MX_KERNEL(cek_sgemm_mxfp4_128x128, 2, 2, 4, 4, 0, GEMM8_E2M1, GEMM8_E2M1)
 // 256×256 tiles, 8 waves (2×4, 128×64 each), balanced-DMA ping-pong, 160 KiB LDS.
-CEK_GEMM4MX_KERNEL(cek_sgemm_mxfp4_256x256pbx, 2, 4, 8, 4, 4)
+CEK_GEMM8_MX_KERNEL(cek_sgemm_mxfp4_256x256pbx, 2, 4, 8, 4, 4, GEMM8_E2M1, GEMM8_E2M1)

@@ -81,16 +81,8 @@
 // covers both.
 #include "gemm8_tile.h"
 
-#define CEK_GEMM8MX_KERNEL(NAME, WM, WN, FM, FN, MODE)                                                          \
-  extern "C" __global__ __launch_bounds__(64 * WM * WN) void NAME(const int* dims, const uint8_t* A,            \
-                                                                    const uint8_t* Bt, const int* SAp,            \
-                                                                    const int* SBp, float* C, CEK_HIDDEN) {       \
-    __shared__ __attribute__((aligned(16))) char smem[gemm8_lds_bytes(WM, WN, FM, FN, MODE)];                    \
-    gemm8_tile<WM, WN, FM, FN, MODE, true, true>(dims, A, Bt, C, smem, __cek_off, SAp, SBp);                     \
-  }
-
 // 128×128 tiles, 4 waves (2×2, 64×64 each), 64 KiB LDS, one stage in flight:
 // the simple kernel the production tile is judged against.
-CEK_GEMM8MX_KERNEL(cek_sgemm_mxfp8_128x128, 2, 2, 4, 4, 0)
+CEK_GEMM8_MX_KERNEL(cek_sgemm_mxfp8_128x128, 2, 2, 4, 4, 0, GEMM8_E4M3, GEMM8_E4M3)
 // 256×256 tiles, 8 waves (2×4, 128×64 each), balanced-DMA ping-pong, 160 KiB LDS.
-CEK_GEMM8MX_KERNEL(cek_sgemm_mxfp8_256x256pbx, 2, 4, 8, 4, 4)
+CEK_GEMM8_MX_KERNEL(cek_sgemm_mxfp8_256x256pbx, 2, 4, 8, 4, 4, GEMM8_E4M3, GEMM8_E4M3)

@@ -21,6 +21,7 @@ the import path for all of them.
 from __future__ import annotations
 
 import weakref
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -184,6 +185,24 @@ MX_OUT_LIB = "sgemm_mx_out"
 MX_OUT_PACK_ID = 0x4D70
 MX_ACTIVATIONS = {None: 0, "relu": 1}  # dims[5]
 
+
+class MxFormat(NamedTuple):
+    """An MX operand format: what an MX GEMM states per operand
+    (``OPERANDS``), and what an ``"mxfp8"`` / ``"mxfp4"`` output mode stores,
+    an output being the next layer's operand."""
+    name: str  # the output mode of a producer whose Y is such an operand
+    dtype: str  # storage dtype of the codes
+    per_item: int  # elements per storage item
+    encode: Callable  # [rows][K] fp32 values -> (what the operand stores, scale bytes)
+    decode: Callable  # (codes, scale bytes) -> values
+    quantizer: type  # the same conversion on the devices (ops/quantize.py)
+    base_id: int  # compute id of its quantise compute for A; +2 for B, +1 for the pack that follows
+
+
+MXFP8 = MxFormat("mxfp8", "float8_e4m3fn", 1, to_mxfp8, from_mxfp8, MxFp8Quantizer, 0x4D58)
+MXFP4 = MxFormat("mxfp4", "float4_e2m1fn_x2", 2, to_mxfp4, from_mxfp4, MxFp4Quantizer, 0x4D60)
+MX_FORMATS = {f.name: f for f in (MXFP8, MXFP4)}
+
 # Mixed MXFP8 × MXFP4 tiles (kernels/sgemm_mxf8f4.hip): A e4m3fn, Bt e2m1, a
 # K-tile of 256 k as two scaled instructions with one format per operand.
 # Throughput beside the MXFP8 256x256pbx of the same run: profiles/gemm_mxf8f4.md.
@@ -303,8 +322,8 @@ class GemmBf16:
         self._orders = {}  # compute id -> shell panels of its tile order (0: grouped)
 
     def _operand_dtype(self, name: str):
-        """Storage dtype of operand ``name`` (``"A"`` / ``"B"``): one for both
-        but in the mixed-format class."""
+        """Storage dtype of operand ``name`` (``"A"`` / ``"B"``); the MX
+        classes read it, like the next, from the operand's :class:`MxFormat`."""
         return self.OPERAND_DTYPE
 
     def _per_item(self, name: str) -> int:
@@ -843,20 +862,17 @@ class GemmMxFp8(GemmBf16):
     K_MULTIPLE = 128
     POSITIVE_DIMS = True
     LIBS = ("sgemm_mxfp8", "mx_quantize")
-    OPERAND_DTYPE = "float8_e4m3fn"
-    _to_mx = staticmethod(to_mxfp8)  # [rows][K] fp32 values -> (what A / B store, scale bytes)
+    OPERANDS = {"A": MXFP8, "B": MXFP8}  # the MX format of each operand
 
-    FORMAT = "mxfp8"  # the output mode of a producer whose Y this class reads as an operand
+    FORMAT = "mxfp8"  # the key of OUT_KERNELS
     OUT_KERNELS = MX_OUT_KERNELS  # (FORMAT, tile, out) -> output-mode kernel, in library OUT_LIB
     OUT_LIB = MX_OUT_LIB
 
-    def _format_of(self, name: str) -> str:
-        """The MX format of operand ``name``: what :meth:`take_operand` asks of a producer."""
-        return self.FORMAT
+    def _operand_dtype(self, name: str):
+        return self.OPERANDS[name].dtype
 
-    def _to_mx_of(self, name: str):
-        """``[rows][K]`` fp32 values -> (what operand ``name`` stores, scale bytes)."""
-        return self._to_mx
+    def _per_item(self, name: str) -> int:
+        return self.OPERANDS[name].per_item
 
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "256x256pbx",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
@@ -894,14 +910,10 @@ class GemmMxFp8(GemmBf16):
         n, per_tile = self.M * self.N, self.BM * self.BN
         self.C = None
         self.SY = self.Yp = None
-        if self.out == "bfloat16":
-            self.Y = ClArray(n, "bfloat16")
-        elif self.out == "mxfp8":
-            self.Y = ClArray(n, "float8_e4m3fn")
-        else:
-            self.Y = ClArray(n // 2, "float4_e2m1fn_x2")
+        fmt = MX_FORMATS.get(self.out)  # None: bf16
+        self.Y = ClArray(n // fmt.per_item, fmt.dtype) if fmt else ClArray(n, "bfloat16")
         self._out_epw = [(self.Y, per_tile * self.Y.N // n // self.L)]
-        if self.out != "bfloat16":
+        if fmt:
             self.SY = ClArray(n // MX_BLOCK, np.uint8)
             self.Yp = ClArray(n // 128, np.uint32)
             self._dims_pack = ClArray(np.array([self.M, self.N], np.int32))
@@ -964,7 +976,7 @@ class GemmMxFp8(GemmBf16):
         for name, arr, sc, rows in (("A", self.A, self.SA, self.M), ("B", self.B, self.SB, self.N)):
             x = rng.uniform(-1, 1, (rows, K // MX_BLOCK, MX_BLOCK))
             x = np.ldexp(x, rng.integers(-12, 13, (rows, K // MX_BLOCK, 1)))
-            codes, scales = self._to_mx_of(name)(x.astype(np.float32).reshape(rows, K))
+            codes, scales = self.OPERANDS[name].encode(x.astype(np.float32).reshape(rows, K))
             arr.array[:] = codes.ravel()
             sc.array[:] = scales.ravel()
 
@@ -1022,7 +1034,7 @@ class GemmMxFp8(GemmBf16):
         they are."""
         if name not in ("A", "B"):
             raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
-        out, fmt = getattr(producer, "out", None), self._format_of(name)
+        out, fmt = getattr(producer, "out", None), self.OPERANDS[name].name
         if out != fmt:
             raise ValueError(f"format mismatch: {type(self).__name__} takes a producer with out={fmt!r} "
                              f"(got out={out!r})")
@@ -1059,15 +1071,14 @@ class GemmMxFp8(GemmBf16):
         ``read`` flag says whether it is uploaded (``False``: it is resident,
         e.g. another kernel of this cruncher wrote it).  ``download=True``
         also brings the codes and scales into ``A`` / ``SA`` (``B`` / ``SB``);
-        otherwise the host arrays are stale until :meth:`sync_operands`."""
-        self._quantize_with(MxFp8Quantizer, 0x4D58, name, x, src, download)
+        otherwise the host arrays are stale until :meth:`sync_operands`.
 
-    def _quantize_with(self, quantizer, base_id: int, name: str, x, src, download: bool) -> None:
-        """:meth:`quantize` with the quantizer class of the format; the
-        operand's quantise and pack computes run under ``base_id`` (A) or
+        The quantizer is that of the operand's format (``OPERANDS``); its
+        quantise and pack computes run under the format's ``base_id`` (A) or
         ``base_id + 2`` (B) and the id after it."""
         if name not in ("A", "B"):
             raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
+        fmt = self.OPERANDS[name]
         rows = self.M if name == "A" else self.N
         n = rows * self.K
         if isinstance(x, ClArray):
@@ -1090,12 +1101,12 @@ class GemmMxFp8(GemmBf16):
             for k in [k for k in self._quantizers if k[0] == name]:  # one quantizer (and input buffer) per operand
                 del self._quantizers[k]
             codes, scales, packed = (self.A, self.SA, self._SAp) if name == "A" else (self.B, self.SB, self._SBp)
-            q = quantizer(rows, self.K, given, cruncher=self.cr, codes=codes, scales=scales, packed=packed,
-                          x=x if isinstance(x, ClArray) else None)
+            q = fmt.quantizer(rows, self.K, given, cruncher=self.cr, codes=codes, scales=scales, packed=packed,
+                              x=x if isinstance(x, ClArray) else None)
             self._quantizers[key] = q
         if not isinstance(x, ClArray):
             q.X.array[:] = x.reshape(-1)
-        base = base_id + (0 if name == "A" else 2)  # compute ids of the quantise and pack computes
+        base = fmt.base_id + (0 if name == "A" else 2)  # compute ids of the quantise and pack computes
         q.run(compute_id=base, upload=upload, download=download, pack_compute_id=base + 1)
         for a in (q.codes, q.scales, q.packed):
             a.read = False  # resident: the next run() must not send the host copy
@@ -1148,10 +1159,10 @@ class GemmMxFp8(GemmBf16):
                 self.cr.download(a, 0)
         if self.out == "bfloat16":
             return from_bf16_bits(self.Y.array).reshape(self.M, self.N)
-        decode, per = (from_mxfp8, 1) if self.out == "mxfp8" else (from_mxfp4, 2)
+        fmt = MX_FORMATS[self.out]
         with np.errstate(over="ignore", invalid="ignore"):
-            return decode(self.Y.array.reshape(self.M, self.N // per),
-                          self.SY.array.reshape(self.M, self.N // MX_BLOCK)).astype(np.float32)
+            return fmt.decode(self.Y.array.reshape(self.M, self.N // fmt.per_item),
+                              self.SY.array.reshape(self.M, self.N // MX_BLOCK)).astype(np.float32)
 
     def verify(self, compute_id: int = 1, tiles_per_device: int = 8, seed: int = 1, host: bool = False) -> float:
         """:meth:`GemmBf16.verify`.  In an output mode: ``max |Y − act(ref)| /
@@ -1217,9 +1228,8 @@ class GemmMxFp4(GemmMxFp8):
     FORMAT = "mxfp4"
     K_MULTIPLE = 256
     LIBS = ("sgemm_mxfp4", "mx4_quantize", "mx_quantize")
-    OPERAND_DTYPE = "float4_e2m1fn_x2"
-    PER_ITEM = 2  # bytes of two elements each
-    _to_mx = staticmethod(to_mxfp4)
+    OPERANDS = {"A": MXFP4, "B": MXFP4}
+    PER_ITEM = MXFP4.per_item  # bytes of two elements each
 
     def quantize(self, *a, **k):
         raise NotImplementedError("GemmMxFp4 takes operands quantised on the host (to_mxfp4): on-device MXFP4 "
@@ -1235,7 +1245,7 @@ class GemmMxFp4(GemmMxFp8):
         byte ``0xFF``).  The packed codes, the row-major scales and the packed
         scales stay resident for the next resident :meth:`run`; the host
         arrays are stale until :meth:`sync_operands` unless ``download``."""
-        self._quantize_with(MxFp4Quantizer, 0x4D60, name, x, src, download)
+        GemmMxFp8.quantize(self, name, x, src, download)
 
 
 class GemmMxFp8Fp4(GemmMxFp8):
@@ -1270,38 +1280,15 @@ class GemmMxFp8Fp4(GemmMxFp8):
 
     TILE_TABLE = MXF8F4_TILES
     TILE_GEOM = MXF8F4_TILE_WAVES
-    FORMAT = "mxf8f4"  # the key of OUT_KERNELS; the operands' formats are _format_of's
+    FORMAT = "mxf8f4"  # the key of OUT_KERNELS; the operands' formats are OPERANDS'
     OUT_KERNELS = MXF8F4_OUT_KERNELS
     OUT_LIB = MXF8F4_OUT_LIB
     K_MULTIPLE = 256
     LIBS = ("sgemm_mxf8f4", "mx_quantize", "mx4_quantize")
-    # per operand: (storage dtype, elements per item, MX format, host codec, quantizer, its base compute id)
-    OPERANDS = {"A": ("float8_e4m3fn", 1, "mxfp8", to_mxfp8, MxFp8Quantizer, 0x4D58),
-                "B": ("float4_e2m1fn_x2", 2, "mxfp4", to_mxfp4, MxFp4Quantizer, 0x4D60)}
+    OPERANDS = {"A": MXFP8, "B": MXFP4}
 
     def __init__(self, M: int, N: int, K: int, devices=None, tile: str = "128x256pbx",
                  cruncher: ClNumberCruncher | None = None, fill: str = "random", seed: int = 0,
                  group_m: int = 4, wave_granularity: bool | None = None, out: str | None = None,
                  act: str | None = None):
         super().__init__(M, N, K, devices, tile, cruncher, fill, seed, group_m, wave_granularity, out, act)
-
-    def _operand_dtype(self, name: str):
-        return self.OPERANDS[name][0]
-
-    def _per_item(self, name: str) -> int:
-        return self.OPERANDS[name][1]
-
-    def _format_of(self, name: str) -> str:
-        return self.OPERANDS[name][2]
-
-    def _to_mx_of(self, name: str):
-        return self.OPERANDS[name][3]
-
-    def quantize(self, name: str, x, src: str | None = None, download: bool = False) -> None:
-        """:meth:`GemmMxFp8.quantize` by the operand's own format: ``"A"`` to
-        MXFP8 (bit for bit :func:`to_mxfp8`), ``"B"`` to MXFP4 (bit for bit
-        :func:`to_mxfp4`), on the devices of this GEMM's cruncher."""
-        if name not in ("A", "B"):
-            raise ValueError(f"operand name must be 'A' or 'B' (got {name!r})")
-        quantizer, base_id = self.OPERANDS[name][4:]
-        self._quantize_with(quantizer, base_id, name, x, src, download)

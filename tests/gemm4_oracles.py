@@ -1,5 +1,5 @@
-"""Cases for the MXFP4 GEMM (kernels/sgemm_mxfp4.hip, gemm8_tile.h with F4,
-ops.gemm.GemmMxFp4), in the manner of gemm8_oracles.py: the shapes, the exact
+"""Cases for the MXFP4 GEMM (kernels/sgemm_mxfp4.hip, gemm8_tile.h with e2m1
+operands, ops.gemm.GemmMxFp4), in the manner of gemm8_oracles.py: the shapes, the exact
 data, the scale-mapping probe with its wrong maps, and the single-instruction
 probe of v_mfma_scale_f32_16x16x128_f8f6f4 with e2m1 operands.
 

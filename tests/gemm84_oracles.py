@@ -1,5 +1,5 @@
 """Cases for the mixed MXFP8 × MXFP4 GEMM (kernels/sgemm_mxf8f4.hip,
-gemm8_tile.h with F4 and A8, ops.gemm.GemmMxFp8Fp4), in the manner of
+gemm8_tile.h with e4m3 A and e2m1 Bt, ops.gemm.GemmMxFp8Fp4), in the manner of
 gemm4_oracles.py: the shapes, the exact data, a numpy emulation of the tile
 under the hypothesised read maps, the scale-mapping probe with its wrong maps,
 and the single-instruction probe of v_mfma_scale_f32_16x16x128_f8f6f4 with an
